@@ -6,6 +6,12 @@ GAE, then 5 epochs x 4 minibatches of the PPO + adaptation update.  value = all 
 (N_gpu x 4096 x 24 x K) / max-over-ranks wall time of the K timed iterations.
 
   python bench.py [--gpus N --steps K --warmup W]           (N > 1: under torch.distributed.run)
+
+A plain run sets up, warms up, times the K iterations and prints the headline line (metric, value, ms_per_step, ...).
+``--dump-outputs DIR`` also writes what the last timed iteration left its caller (policy parameters, the rollout's
+arrays, the env's observations) as DIR/<name>.npy.  ``--full`` adds every other figure: the env kernel's and the
+update GEMM's launch times and rooflines, the self-contact statistics, the env-only rate, the Go1 rough-terrain line
+(``secondary``) and the CPU baseline.
 """
 import argparse
 import json
@@ -263,13 +269,106 @@ def check_rank_devices(world, rank, local_dev, backend):
     return devices
 
 
+def full_figures(args, elapsed, k_ms, g_ms, g_n, sc, env_only):
+    """``--full``: the result line's figures beside the headline, from the launch times the timed iterations recorded
+    (k_ms: mean env-kernel ms; g_ms over g_n launches of the update's largest GEMM), the self-contact counters and the
+    env-only rate."""
+    from lrl.ppo import runner as R
+    achieved = B_ENV * ENVS_PER_GPU / (k_ms * 1e-3) / 1e9
+    traffic, traffic_src = pmc_traffic("lrl::flat::env_step_kernel<false>", "lrl::env_step_kernel<false>")
+    # update's largest product: actor/critic layer-2 weight gradient, 2 x (256 x 512) over the minibatch rows
+    mb_rows = ENVS_PER_GPU * R.RunnerArgs.num_steps_per_env // 4
+    gemm_flop = 2.0 * 2 * 256 * 512 * mb_rows
+    gemm_ms = g_ms / max(1, g_n)
+    gemm_tf = gemm_flop / (gemm_ms * 1e-3) / 1e12 if g_n else None
+    # dW2 has its own symbol (trace tag 1, csrc/lrl_gemm.hip tn_shape_tag: the LDS-DMA x6t kernel since round 4, the
+    # x6 kernel in round 3): its PMC row is this launch's traffic
+    gemm_kernel = "lrl::gemm_x6t_kernel<128, 1, false>"
+    gemm_traffic, gemm_traffic_src = pmc_traffic(gemm_kernel, "lrl::gemm_x6t_kernel<1, false>",
+                                                 "lrl::gemm_x6_kernel<128, 128, 3, 4, true, false, 1>")
+    # whole iteration against the fp32 MFMA peak: SURVEY.md §8(d)'s 3.92 MFLOP per minibatch row and epoch of
+    # the update (5 epochs over the 98,304 rollout rows) + 0.94 MFLOP per rollout row of the act
+    rows_iter = ENVS_PER_GPU * R.RunnerArgs.num_steps_per_env
+    iter_flop = rows_iter * (5 * 3.92e6 + 0.94e6)
+    iter_tf = iter_flop / (elapsed / args.steps) / 1e12
+    return {
+        "env_only_env_steps_per_s_per_gpu": round(env_only, 1),
+        "env_step_kernel_ms": round(k_ms, 4),
+        "self_contact": dict(sc, note="one untimed PPO iteration after the timed ones; a pair without a slot is "
+                                      "one PhysX would solve and this solver skips in that sub-step (DESIGN.md §4)"),
+        "roofline": {"bound": "hbm", "kernel": "lrl::flat::env_step_kernel<false> (plane ground)", "achieved": round(achieved, 3),
+                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
+                     "traffic": round(traffic) if traffic else None, "traffic_source": traffic_src,
+                     "note": f"algorithmic {B_ENV} B/env-step x {ENVS_PER_GPU} envs per launch (+ the newest history "
+                             f"slot, 168 B/env-step; the older slots move in the separate shift_history_kernel launch "
+                             "before it); the kernel is latency-bound (16 lanes per env = 4 mirrored quads, one single-wave "
+                             "workgroup per 4 envs, 1,024 waves; the slowest wave sets the launch), see DESIGN.md"},
+        "roofline_update_gemm": {
+            "bound": "mfma", "kernel": f"{gemm_kernel} (dW2: 2 x 256x512, {mb_rows} rows)",
+            "achieved": round(gemm_tf, 2) if gemm_tf else None, "peak": round(X6_PEAK_TF, 1),
+            "unit": "TFLOP/s", "frac": round(gemm_tf / X6_PEAK_TF, 4) if gemm_tf else None,
+            "arithmetic": "fp32 operands split exactly into 3 bf16 parts, 6 bf16 MFMA products per k-step, fp32 "
+                          "accumulation (error at the fp32 level, tests/test_gemm_gpu.py); peak = dense bf16 MFMA "
+                          f"{MFMA_BF16_PEAK_TF:.0f} TF / 6 (the fp32 MFMA peak is {MFMA_F32_PEAK_TF} TF)",
+            "traffic": round(gemm_traffic) if gemm_traffic else None, "traffic_source": gemm_traffic_src,
+            "algorithmic_bytes": 4 * (2 * mb_rows * (256 + 512)),
+            "launch_ms": round(gemm_ms, 4), "launches": g_n,
+            "note": "the GEMM family is ~70% of the iteration's GPU time; this is its largest launch "
+                    "(split-k partials written to the workspace count in traffic)"},
+        "roofline_iteration": {
+            "bound": "mfma", "achieved": round(iter_tf, 2), "peak": round(X6_PEAK_TF, 1), "unit": "TFLOP/s",
+            "frac": round(iter_tf / X6_PEAK_TF, 4), "flop_per_iteration": iter_flop,
+            "note": "SURVEY.md §8(d): 3.92 MFLOP per row and epoch (update) + 0.94 MFLOP per rollout row; "
+                    "the env step's work is not counted"},
+    }
+
+
+DUMP_ARRAY_BYTES = 16 << 20   # a larger array is written as a fixed, seeded sample of its rows
+DUMP_TOTAL_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, runner, env):
+    """``--dump-outputs``: what the last timed iteration of Runner.learn left its caller, as <path>/<name>.npy (float32):
+    ``policy.<parameter>`` the actor-critic's state dict after the iteration's update, ``rollout.<field>`` the iteration's
+    rollout arrays (steps x envs x ...; returns and advantages as GAE left them) and ``env.<buffer>`` the observations the
+    next act would read.  The seeds are fixed, so two runs with the same arguments start from the same inputs.  An array
+    over DUMP_ARRAY_BYTES is cut to a seeded sample of its rows (leading dimensions flattened; ``<name>.rows.npy`` holds
+    their indices)."""
+    os.makedirs(path, exist_ok=True)
+    s = runner.alg.storage
+    obs = env.get_observations()
+    arrays = {f"policy.{k}": v for k, v in runner.alg.actor_critic.state_dict().items()}
+    arrays.update({f"rollout.{k}": getattr(s, k) for k in ("actions", "mu", "sigma", "actions_log_prob", "values",
+                                                           "rewards", "dones", "returns", "advantages")})
+    arrays.update({f"env.{k}": obs[k] for k in ("obs", "privileged_obs", "obs_history")})
+    total = 0
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
+        if a.nbytes > DUMP_ARRAY_BYTES:
+            a = a.reshape(-1, a.shape[-1])
+            keep = DUMP_ARRAY_BYTES // (4 * a.shape[1])
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            np.save(os.path.join(path, name + ".rows.npy"), rows.astype(np.float64))
+            total += 8 * rows.size
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_TOTAL_BYTES, f"--dump-outputs wrote {total} bytes"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the Go1 rough-terrain line (configs[2])")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (rank 0's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: kernel launch times + rooflines, self-contact "
+                         "statistics, env-only rate, the Go1 rough-terrain line and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the Go1 rough-terrain line (configs[2])")
     ap.add_argument("--workload", choices=["mc", "go1"], default="mc",
                     help="mc: 4096 Mini Cheetah envs per GPU, flat (configs[1] / [3]); go1: 4096 Go1 envs per GPU, "
                          "plane, teacher + student update (configs[4] at --gpus 2)")
@@ -326,6 +425,9 @@ def main():
     cfg.env.num_envs = ENVS_PER_GPU
     R.RunnerArgs.save_interval = 0
     R.RunnerArgs.log_freq = 10 ** 9
+    # the policy's initial weights, the random episode lengths and the update's minibatch permutations come from torch's
+    # default generators: seeded (alike on every rank, as DDP would broadcast the weights), a run repeats its inputs
+    torch.manual_seed(1234)
     env = HistoryWrapper(LeggedRobotEnv(dev, cfg=cfg, seed=1234, env_offset=rank * ENVS_PER_GPU))
     g = torch.Generator(device=dev).manual_seed(1 + rank)
     cmd = torch.rand(ENVS_PER_GPU, 3, device=dev, generator=g)
@@ -337,62 +439,51 @@ def main():
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    env_kernel_timing(env.env, True)
     import ctypes as C
     from lrl import _abi
-    _abi.check(_abi.lib().lrl_ppo_timing(1, None, None))  # events around the update's largest GEMM
+    if args.full:  # HIP events around each env-kernel launch and around the update's largest GEMM (the rooflines)
+        env_kernel_timing(env.env, True)
+        _abi.check(_abi.lib().lrl_ppo_timing(1, None, None))
     t0 = time.perf_counter()
     runner.learn(args.steps)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     g_ms, g_n = C.c_double(0.0), C.c_int64(0)
-    _abi.check(_abi.lib().lrl_ppo_timing(0, C.byref(g_ms), C.byref(g_n)))
+    if args.full:
+        _abi.check(_abi.lib().lrl_ppo_timing(0, C.byref(g_ms), C.byref(g_n)))
     if world > 1:
         dist.barrier()
-    k_ms = env_kernel_timing(env.env, False)
+    k_ms = env_kernel_timing(env.env, False) if args.full else None
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
-    # self-contact slot statistics under the bench's own workload (one more, untimed, iteration with the counters on)
-    env.env.self_contact_stats(True)
-    runner.learn(1)
-    torch.cuda.synchronize()
-    sc = env.env.self_contact_stats(False)
-    sc["env_substeps"] = ENVS_PER_GPU * R.RunnerArgs.num_steps_per_env * 4
-    sc["dropped_fraction_of_pairs"] = sc["self_pairs_dropped"] / max(1, sc["self_pairs_in_contact"])
-    # env-only rate: the fused step kernel alone, random actions, same env
-    a = torch.randn(ENVS_PER_GPU, 12, device=dev) * 0.3
-    for _ in range(10):
-        env.step(a)
-    torch.cuda.synchronize()
-    te = time.perf_counter()
-    ne = 100
-    for _ in range(ne):
-        env.step(a)
-    torch.cuda.synchronize()
-    env_only = ENVS_PER_GPU * ne / (time.perf_counter() - te)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, runner, env)
+    sc = env_only = None
+    if args.full:
+        # self-contact slot statistics under the bench's own workload (one more, untimed, iteration, counters on)
+        env.env.self_contact_stats(True)
+        runner.learn(1)
+        torch.cuda.synchronize()
+        sc = env.env.self_contact_stats(False)
+        sc["env_substeps"] = ENVS_PER_GPU * R.RunnerArgs.num_steps_per_env * 4
+        sc["dropped_fraction_of_pairs"] = sc["self_pairs_dropped"] / max(1, sc["self_pairs_in_contact"])
+        # env-only rate: the fused step kernel alone, random actions, same env
+        a = torch.randn(ENVS_PER_GPU, 12, device=dev) * 0.3
+        for _ in range(10):
+            env.step(a)
+        torch.cuda.synchronize()
+        te = time.perf_counter()
+        ne = 100
+        for _ in range(ne):
+            env.step(a)
+        torch.cuda.synchronize()
+        env_only = ENVS_PER_GPU * ne / (time.perf_counter() - te)
 
     steps_total = world * ENVS_PER_GPU * R.RunnerArgs.num_steps_per_env * args.steps
     value = steps_total / elapsed
     if rank == 0:
-        achieved = B_ENV * ENVS_PER_GPU / (k_ms * 1e-3) / 1e9
-        traffic, traffic_src = pmc_traffic("lrl::flat::env_step_kernel<false>", "lrl::env_step_kernel<false>")
-        # update's largest product: actor/critic layer-2 weight gradient, 2 x (256 x 512) over the minibatch rows
-        mb_rows = ENVS_PER_GPU * R.RunnerArgs.num_steps_per_env // 4
-        gemm_flop = 2.0 * 2 * 256 * 512 * mb_rows
-        gemm_ms = g_ms.value / max(1, g_n.value)
-        gemm_tf = gemm_flop / (gemm_ms * 1e-3) / 1e12 if g_n.value else None
-        # dW2 has its own symbol (trace tag 1, csrc/lrl_gemm.hip tn_shape_tag: the LDS-DMA x6t kernel since round 4, the
-        # x6 kernel in round 3): its PMC row is this launch's traffic
-        gemm_kernel = "lrl::gemm_x6t_kernel<128, 1, false>"
-        gemm_traffic, gemm_traffic_src = pmc_traffic(gemm_kernel, "lrl::gemm_x6t_kernel<1, false>",
-                                                     "lrl::gemm_x6_kernel<128, 128, 3, 4, true, false, 1>")
-        # whole iteration against the fp32 MFMA peak: SURVEY.md §8(d)'s 3.92 MFLOP per minibatch row and epoch of
-        # the update (5 epochs over the 98,304 rollout rows) + 0.94 MFLOP per rollout row of the act
-        rows_iter = ENVS_PER_GPU * R.RunnerArgs.num_steps_per_env
-        iter_flop = rows_iter * (5 * 3.92e6 + 0.94e6)
-        iter_tf = iter_flop / (elapsed / args.steps) / 1e12
         # distinct physical devices the ranks ran on (a gloo rehearsal puts several ranks on one GPU)
         n_dev = world if backend == "nccl" else min(world, ndev)
         out = {
@@ -410,41 +501,15 @@ def main():
                        "backend": (backend if dist.is_initialized() else None), "devices": devices,
                        "policy": "ActorCritic 42/18/630->12, random init; teacher PPO + student adaptation update"},
             "ppo_iters_per_s": round(args.steps / elapsed, 3),
-            "env_only_env_steps_per_s_per_gpu": round(env_only, 1),
-            "env_step_kernel_ms": round(k_ms, 4),
-            "self_contact": dict(sc, note="one untimed PPO iteration after the timed ones; a pair without a slot is "
-                                          "one PhysX would solve and this solver skips in that sub-step (DESIGN.md §4)"),
-            "roofline": {"bound": "hbm", "kernel": "lrl::flat::env_step_kernel<false> (plane ground)", "achieved": round(achieved, 3),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
-                         "traffic": round(traffic) if traffic else None, "traffic_source": traffic_src,
-                         "note": f"algorithmic {B_ENV} B/env-step x {ENVS_PER_GPU} envs per launch (+ the newest history "
-                                 f"slot, 168 B/env-step; the older slots move in the separate shift_history_kernel launch "
-                                 "before it); the kernel is latency-bound (16 lanes per env = 4 mirrored quads, one single-wave "
-                                 "workgroup per 4 envs, 1,024 waves; the slowest wave sets the launch), see DESIGN.md"},
-            "roofline_update_gemm": {
-                "bound": "mfma", "kernel": f"{gemm_kernel} (dW2: 2 x 256x512, {mb_rows} rows)",
-                "achieved": round(gemm_tf, 2) if gemm_tf else None, "peak": round(X6_PEAK_TF, 1),
-                "unit": "TFLOP/s", "frac": round(gemm_tf / X6_PEAK_TF, 4) if gemm_tf else None,
-                "arithmetic": "fp32 operands split exactly into 3 bf16 parts, 6 bf16 MFMA products per k-step, fp32 "
-                              "accumulation (error at the fp32 level, tests/test_gemm_gpu.py); peak = dense bf16 MFMA "
-                              f"{MFMA_BF16_PEAK_TF:.0f} TF / 6 (the fp32 MFMA peak is {MFMA_F32_PEAK_TF} TF)",
-                "traffic": round(gemm_traffic) if gemm_traffic else None, "traffic_source": gemm_traffic_src,
-                "algorithmic_bytes": 4 * (2 * mb_rows * (256 + 512)),
-                "launch_ms": round(gemm_ms, 4), "launches": g_n.value,
-                "note": "the GEMM family is ~70% of the iteration's GPU time; this is its largest launch "
-                        "(split-k partials written to the workspace count in traffic)"},
-            "roofline_iteration": {
-                "bound": "mfma", "achieved": round(iter_tf, 2), "peak": round(X6_PEAK_TF, 1), "unit": "TFLOP/s",
-                "frac": round(iter_tf / X6_PEAK_TF, 4), "flop_per_iteration": iter_flop,
-                "note": "SURVEY.md §8(d): 3.92 MFLOP per row and epoch (update) + 0.94 MFLOP per rollout row; "
-                        "the env step's work is not counted"},
             "reference_context": {"upstream_example_run_env_steps_per_s": 41176, "upstream_ppo_iters_per_s": 0.429,
                                   "hardware": "unspecified NVIDIA GPU, 4000 envs (BASELINE.md §1)"},
         }
-        if world == 1 and not args.no_secondary:
+        if args.full:
+            out.update(full_figures(args, elapsed, k_ms, g_ms.value, g_n.value, sc, env_only))
+        if args.full and world == 1 and not args.no_secondary:
             env.env.close()
             out["secondary"] = bench_go1_rough(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), file=json_out, flush=True)
     if dist.is_initialized():

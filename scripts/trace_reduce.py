@@ -1,7 +1,7 @@
 """Per (kernel, grid) mean duration from a rocprofv3 --kernel-trace CSV (distinguishes the GEMMs of the
 update by their grid).  ``tail_mean_us`` averages only each kernel's last TAIL launches (env TAIL, default 120 =
 bench.py's 5 timed iterations x 24 env steps), i.e. the launches of bench.py's timed region, which is what its
-HIP-event ``env_step_kernel_ms`` averages.  usage: python scripts/trace_reduce.py <kernel_trace.csv> [name-filter]"""
+HIP-event ``env_step_kernel_ms`` (a ``--full`` figure) averages.  usage: python scripts/trace_reduce.py <kernel_trace.csv> [name-filter]"""
 import os
 import csv
 import sys

@@ -47,7 +47,7 @@ def test_library_matches_the_sources_beside_it():
         _abi.source_hash, _abi._lib = real, saved
 
 
-def test_struct_layout_matches_header():
+def test_struct_layout_matches_header(tmp_path):
     code = r"""
 #include <stdio.h>
 #include <stddef.h>
@@ -60,9 +60,10 @@ printf("%zu %zu\n", offsetof(lrl_ppo_batch, hist_ld), offsetof(lrl_rollout_store
 printf("%zu %zu %zu\n", sizeof(lrl_dev_curriculum), offsetof(lrl_dev_curriculum, nz), offsetof(lrl_dev_curriculum, draws));
 return 0;}
 """
-    exe = "/tmp/lrl_layout_check"
+    exe = str(tmp_path / "lrl_layout_check")
     src = exe + ".c"
-    open(src, "w").write(code)
+    with open(src, "w") as f:
+        f.write(code)
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, src])
     out = [int(x) for x in subprocess.check_output([exe]).split()]
     assert out == [C.sizeof(_abi.LrlModel), C.sizeof(_abi.LrlEnvParams), C.sizeof(_abi.LrlTensor),

@@ -3,6 +3,7 @@ a mocked torch.distributed and a mocked liblrl: per optimiser step exactly one a
 (its KL slot included — the adaptive learning rate's all-reduced KL mean rides in it), one of the adaptation
 module's gradient per adaptation substep, and one of the advantage statistics per iteration; nothing else.
 (ppo.py:94-178 / rollout_storage.py:76-90 of the reference run on one device; this is the data-parallel form.)"""
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -43,6 +44,8 @@ def test_native_update_issues_one_flat_gradient_allreduce_per_optimizer_step(mon
     monkeypatch.setattr(_abi, "stream_of", lambda dev: C.c_void_p(0))
     cur = object()
     monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: cur)
+    # (with a GPU visible torch.cuda.stream would switch to the mocked stream; without one it is a no-op already)
+    monkeypatch.setattr(torch.cuda, "stream", lambda s: contextlib.nullcontext())
     monkeypatch.setattr(P.PPO_Args, "num_adaptation_module_substeps", substeps)
     ac = ActorCritic(42, 18, 630, 12)
     alg = P.PPO(ac, device="cpu", fused=True)

@@ -2,7 +2,7 @@
 hulls (mini_cheetah.urdf:119-124, 176-181), and the rod boxes of both presets' thighs / calves meet the plane at the
 support point a cube-map table gives (lrl/robot.py support_table).  Checked here: the tables reproduce each hull's support function within 1 mm, the
 oracle's lookup (lrl_oracle.c hull_support) picks the table's point, the model carries the tables through the C ABI,
-and (in this container only) the committed tables are the ones the builder makes from the reference's meshes."""
+and the committed tables are the ones the builder makes from the reference's meshes."""
 import ctypes as C
 import os
 
@@ -113,12 +113,12 @@ def test_straight_down_support_point():
         assert abs(p[2] - exact) < 1e-3
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/resources/robots/mini_cheetah"),
-                    reason="reference meshes only in the build container")
-def test_committed_tables_are_the_builders():
-    """scripts/make_robot_tables.py's tables from the reference meshes equal the committed .npz"""
+def test_committed_tables_are_the_builders(golden_dir):
+    """scripts/make_robot_tables.py's tables from the reference meshes equal the committed .npz.  The meshes are the
+    fixtures under tests/golden/mini_cheetah: the preset's URDF and the vertex lines of its two collision meshes (the
+    ab/ad and the lower link; the builder reads nothing else of an .obj)."""
     from lrl.robot import build_quadruped
-    m = build_quadruped("/root/reference/resources/robots/mini_cheetah/urdf/mini_cheetah.urdf")
+    m = build_quadruped(os.path.join(golden_dir, "mini_cheetah", "urdf", "mini_cheetah.urdf"))
     rob = load_robot("mini_cheetah.urdf")
     assert m["sphere_hull"] == rob["sphere_hull"]
     for h, v in enumerate(m["hull_vertices"]):
