@@ -483,6 +483,12 @@ typedef struct lrl_ppo_net {
   int64_t adapt_begin, adapt_end; /* parameters of the adaptation step */
   int64_t kl_slot;                /* grads[kl_slot] = minibatch KL mean (all-reduced with the grads) */
   int64_t total;                  /* buffer length */
+  /* appended fields: a zero-initialised descriptor keeps the ELU teacher / student form */
+  int32_t activation; /* hidden activation: 0 = ELU, 1 = tanh (supported with plain = 1 only) */
+  int32_t plain;      /* 1 = plain MLP actor / critic over the observations alone (the high-level navigation policy):
+                       * latent = enc_h* = ad_h* = 0, adapt_begin == adapt_end, the e* / d* offsets are unused and
+                       * num_priv / num_hist are carried but not read; num_actions is 3 or 12.  lrl_ppo_act takes
+                       * priv == hist == NULL; the adaptation calls and lrl_ppo_act_student refuse such a net. */
 } lrl_ppo_net;
 
 /* One minibatch: the flattened rollout storage ([T*N, .]) and the minibatch's row indices (the int64
@@ -586,7 +592,8 @@ int32_t lrl_debug_sim_arena(lrl_sim* s, void** arena, int64_t* bytes, int64_t* s
 /* Test entry point of the GEMM the update is built from: C = op(A) op(B) with
  * layout 0 (NT: C[m][n] = sum_k A[m][k] B[n][k]), 2 (NN: sum_k A[m][k] B[k][n]),
  * 3 (TN: sum_k A[k][m] B[k][n], split over k, partials reduced in place);
- * epi 0 store, 1 +bias[n], 2 elu(+bias[n]), 3 *elu'(aux[m][n]).  rows (optional) gathers A's rows
+ * epi 0 store, 1 +bias[n], 2 elu(+bias[n]), 3 *elu'(aux[m][n]), 5 tanh(+bias[n]) (NT only), 6 *(1 - aux[m][n]^2)
+ * (NN only; aux = the tanh output of the layer input).  rows (optional) gathers A's rows
  * (NT/NN) or B's rows (TN).  layout | 0x100 (NT / NN): B is first split into hi / mid / lo bf16 planes in the
  * workspace (3 * N * round16(K) / 2 floats) and the product runs on the pre-split-B kernel the update uses for its
  * weight products, or fails if the shape is not one it takes. */

@@ -37,6 +37,8 @@ enum GemmEpi : int {
   EPI_BIAS_ELU = 2,  // C = elu(acc + bias[n])
   EPI_DELU = 3,      // C = acc * elu'(aux[m][n])  (aux = ELU output of the layer input: elu' = aux > 0 ? 1 : aux + 1)
   EPI_PARTIAL = 4,   // split-k partial: C + split * part_stride (+ bias-gradient partial of A's columns)
+  EPI_BIAS_TANH = 5, // C = tanh(acc + bias[n])  (NT products only)
+  EPI_DTANH = 6,     // C = acc * (1 - aux[m][n]^2)  (NN products only; aux = tanh output of the layer input)
 };
 
 struct GemmP {

@@ -57,6 +57,13 @@ static int tn_shape_tag(int M, int N, int groups) {
 }
 
 __device__ __forceinline__ float elu_f(float x) { return x > 0.f ? x : expm1f(x); }
+// the device library's tanhf: an odd polynomial below |x| = 0.625, so small pre-activations keep their relative
+// accuracy (a bare 1 - 2 / (exp(2x) + 1) cancels there: half the digits are gone at |x| = 1e-3), and the function torch
+// itself evaluates on the device
+__device__ __forceinline__ float tanh_f(float x) { return tanhf(x); }
+// epilogue classes: a bias vector added before the activation / the layer input's activation output read as aux
+__host__ __device__ constexpr bool epi_bias(int e) { return e == EPI_BIAS || e == EPI_BIAS_ELU || e == EPI_BIAS_TANH; }
+__host__ __device__ constexpr bool epi_aux(int e) { return e == EPI_DELU || e == EPI_DTANH; }
 
 // load 4 consecutive floats (all in range) with the widest access the operand's alignment allows
 __device__ __forceinline__ float4 load4(const float* __restrict__ src, int vec) {
@@ -225,8 +232,8 @@ __global__ __launch_bounds__(GTHREADS) void gemm_kernel(GemmP p) {
   const bool fast = m0 + BM <= p.M && n0 + BN <= p.N && ((kend - kbeg) % GBK) == 0 && p.avec == 4 && p.bvec == 4;
   // backward-data epilogue operand (the layer input, for elu'): fetched up front so its latency hides
   // under the main loop instead of trailing it
-  float xaux[EPI == EPI_DELU ? TM : 1][EPI == EPI_DELU ? TN : 1][16];
-  if constexpr (EPI == EPI_DELU) {
+  float xaux[epi_aux(EPI) ? TM : 1][epi_aux(EPI) ? TN : 1][16];
+  if constexpr (epi_aux(EPI)) {
     const float* __restrict__ ax = p.aux + g * p.gaux;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -314,7 +321,7 @@ __global__ __launch_bounds__(GTHREADS) void gemm_kernel(GemmP p) {
     const int col = n0 + wn + 32 * j + li;
     if (col >= p.N) continue;
     float bj = 0.f;
-    if (EPI == EPI_BIAS || EPI == EPI_BIAS_ELU) bj = bias[col];
+    if (epi_bias(EPI)) bj = bias[col];
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -324,9 +331,10 @@ __global__ __launch_bounds__(GTHREADS) void gemm_kernel(GemmP p) {
           float v = NACC == 2 ? acc[i][j][r] + acc2[i][j][r] : acc[i][j][r];
           if (EPI == EPI_BIAS) v += bj;
           if (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
-          if constexpr (EPI == EPI_DELU) {
+          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
+          if constexpr (epi_aux(EPI)) {
             const float x = xaux[i][j][r];
-            v = x > 0.f ? v : v * (x + 1.f);
+            v = EPI == EPI_DTANH ? v * (1.f - x * x) : (x > 0.f ? v : v * (x + 1.f));
           }
           C[(int64_t)row * p.ldc + col] = v;
         }
@@ -400,7 +408,7 @@ __global__ __launch_bounds__(GTHREADS) void gemm_glds_kernel(GemmP p) {
 
   // backward-data epilogue operand (elu' of the layer input), fetched before the DMA ring starts
   float xaux[16];
-  if constexpr (EPI == EPI_DELU) {
+  if constexpr (epi_aux(EPI)) {
     const float* __restrict__ ax = p.aux + g * p.gaux;
     const int col = n0 + wn + li;
 #pragma unroll
@@ -457,16 +465,17 @@ __global__ __launch_bounds__(GTHREADS) void gemm_glds_kernel(GemmP p) {
   float* __restrict__ C = p.C + g * p.gc;
   const int col = n0 + wn + li;
   float bj = 0.f;
-  if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_ELU) bj = p.bias[g * p.gbias + col];
+  if constexpr (epi_bias(EPI)) bj = p.bias[g * p.gbias + col];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * h;
     float v = acc[r] + acc2[r];
     if constexpr (EPI == EPI_BIAS) v += bj;
     if constexpr (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
-    if constexpr (EPI == EPI_DELU) {
+          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
+    if constexpr (epi_aux(EPI)) {
       const float x = xaux[r];
-      v = x > 0.f ? v : v * (x + 1.f);
+      v = EPI == EPI_DTANH ? v * (1.f - x * x) : (x > 0.f ? v : v * (x + 1.f));
     }
     C[(int64_t)row * p.ldc + col] = v;
   }
@@ -527,7 +536,7 @@ __global__ __launch_bounds__(GTHREADS) void gemm_glds32_kernel(GemmP p) {
     }
   };
   float xaux[16];
-  if constexpr (EPI == EPI_DELU) {
+  if constexpr (epi_aux(EPI)) {
     const float* __restrict__ ax = p.aux + g * p.gaux;
     const int col = n0 + wn + li;
 #pragma unroll
@@ -581,16 +590,17 @@ __global__ __launch_bounds__(GTHREADS) void gemm_glds32_kernel(GemmP p) {
   float* __restrict__ C = p.C + g * p.gc;
   const int col = n0 + wn + li;
   float bj = 0.f;
-  if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_ELU) bj = p.bias[g * p.gbias + col];
+  if constexpr (epi_bias(EPI)) bj = p.bias[g * p.gbias + col];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * h;
     float v = acc[r] + acc2[r];
     if constexpr (EPI == EPI_BIAS) v += bj;
     if constexpr (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
-    if constexpr (EPI == EPI_DELU) {
+          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
+    if constexpr (epi_aux(EPI)) {
       const float x = xaux[r];
-      v = x > 0.f ? v : v * (x + 1.f);
+      v = EPI == EPI_DTANH ? v * (1.f - x * x) : (x > 0.f ? v : v * (x + 1.f));
     }
     C[(int64_t)row * p.ldc + col] = v;
   }
@@ -665,7 +675,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_thin_kernel(GemmP p) {
     __syncthreads();
     if (w == 0) {
       float bj = 0.f;
-      if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_ELU) bj = colv ? p.bias[g * p.gbias + li] : 0.f;
+      if constexpr (epi_bias(EPI)) bj = colv ? p.bias[g * p.gbias + li] : 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         float v = acc[r] + acc2[r];
@@ -674,6 +684,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_thin_kernel(GemmP p) {
         v += red[(32 + r) * 64 + lane];
         if constexpr (EPI == EPI_BIAS) v += bj;
         if constexpr (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
+          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
         const int orow = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
         if (colv && orow < M) C[(int64_t)orow * p.ldc + li] = v;
       }
@@ -757,7 +768,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_thin16_kernel(GemmP p) {
       for (int cb = 0; cb < 2; ++cb) {
         const int col = i + 16 * cb;
         float bj = 0.f;
-        if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_ELU) bj = col < N ? p.bias[g * p.gbias + col] : 0.f;
+        if constexpr (epi_bias(EPI)) bj = col < N ? p.bias[g * p.gbias + col] : 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float v = cb ? acc1[r] : acc0[r];
@@ -766,6 +777,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_thin16_kernel(GemmP p) {
           v += red[(16 + 4 * cb + r) * 64 + lane];
           if constexpr (EPI == EPI_BIAS) v += bj;
           if constexpr (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
+          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
           const int orow = t * 16 + 4 * h + r;
           if (col < N && orow < M) C[(int64_t)orow * p.ldc + col] = v;
         }
@@ -1290,13 +1302,13 @@ __global__ __launch_bounds__(GTHREADS, 3) void gemm_x6_kernel(GemmP p) {  // 3 w
   const float* __restrict__ bias = p.bias ? p.bias + g * p.gbias : nullptr;
   // (the backward-data epilogue's layer input is read here, not prefetched: 16 registers per MFMA tile held
   // through the main loop would cost occupancy)
-  const float* __restrict__ ax = EPI == EPI_DELU ? p.aux + g * p.gaux : nullptr;
+  const float* __restrict__ ax = epi_aux(EPI) ? p.aux + g * p.gaux : nullptr;
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int col = n0 + wn + 32 * j + li;
     if (!FAST && col >= p.N) continue;
     float bj = 0.f;
-    if (EPI == EPI_BIAS || EPI == EPI_BIAS_ELU) bj = bias[col];
+    if (epi_bias(EPI)) bj = bias[col];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1306,7 +1318,7 @@ __global__ __launch_bounds__(GTHREADS, 3) void gemm_x6_kernel(GemmP p) {  // 3 w
         const int ldc = (int)p.ldc, ldx = (int)p.ld_aux;
         float* __restrict__ crow = C + (int64_t)row0 * p.ldc + col;
         float xa[4];
-        if constexpr (EPI == EPI_DELU) {
+        if constexpr (epi_aux(EPI)) {
           const float* __restrict__ xrow = ax + (int64_t)row0 * p.ld_aux + col;
 #pragma unroll
           for (int r = 0; r < 4; ++r) xa[r] = (FAST || row0 + r < p.M) ? xrow[r * ldx] : 0.f;
@@ -1317,9 +1329,10 @@ __global__ __launch_bounds__(GTHREADS, 3) void gemm_x6_kernel(GemmP p) {  // 3 w
             float v = acc[i][j][4 * q + r];
             if (EPI == EPI_BIAS) v += bj;
             if (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
-            if constexpr (EPI == EPI_DELU) {
+          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
+            if constexpr (epi_aux(EPI)) {
               const float x = xa[r];
-              v = x > 0.f ? v : v * (x + 1.f);
+              v = EPI == EPI_DTANH ? v * (1.f - x * x) : (x > 0.f ? v : v * (x + 1.f));
             }
             crow[r * ldc] = v;
           }
@@ -1361,10 +1374,12 @@ static int launch_x6_tile(const GemmP& p, int layout, int epi, int groups, hipSt
     if (epi == EPI_STORE) LRL_X6(GEMM_NT, EPI_STORE);
     else if (epi == EPI_BIAS) LRL_X6(GEMM_NT, EPI_BIAS);
     else if (epi == EPI_BIAS_ELU) LRL_X6(GEMM_NT, EPI_BIAS_ELU);
+    else if (epi == EPI_BIAS_TANH) LRL_X6(GEMM_NT, EPI_BIAS_TANH);
     else return LRL_E_INVALID;
   } else if (layout == GEMM_NN) {
     if (epi == EPI_STORE) LRL_X6(GEMM_NN, EPI_STORE);
     else if (epi == EPI_DELU) LRL_X6(GEMM_NN, EPI_DELU);
+    else if (epi == EPI_DTANH) LRL_X6(GEMM_NN, EPI_DTANH);
     else return LRL_E_INVALID;
   } else if (layout == GEMM_TN && epi == EPI_PARTIAL) {
     const int tag = (BM == 128 && BN == 128 && interior) ? tn_shape_tag(p.M, p.N, groups) : 0;
@@ -1406,7 +1421,7 @@ static int try_x6(const GemmP& p, int layout, int epi, int groups, hipStream_t s
   const int64_t lim = int64_t(1) << 31;
   if ((layout & 1) && (int64_t)p.K * p.lda >= lim) return 0;
   if ((layout & 2) && p.b_rows == nullptr && (int64_t)p.K * p.ldb >= lim) return 0;
-  if ((int64_t)p.M * p.ldc >= lim || (epi == EPI_DELU && (int64_t)p.M * p.ld_aux >= lim)) return 0;
+  if ((int64_t)p.M * p.ldc >= lim || (epi_aux(epi) && (int64_t)p.M * p.ld_aux >= lim)) return 0;
   int rc;
   if (layout == GEMM_TN) {
     // (both operands r-contiguous: dword loads, any alignment)
@@ -1568,12 +1583,12 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6p_kernel(GemmP p) {
 
   float* __restrict__ C = p.C + g * p.gc;
   const float* __restrict__ bias = p.bias ? p.bias + g * p.gbias : nullptr;
-  const float* __restrict__ ax = EPI == EPI_DELU ? p.aux + g * p.gaux : nullptr;
+  const float* __restrict__ ax = epi_aux(EPI) ? p.aux + g * p.gaux : nullptr;
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int col = n0 + wn + 32 * j + li;
     float bj = 0.f;
-    if (EPI == EPI_BIAS || EPI == EPI_BIAS_ELU) bj = bias[col];
+    if (epi_bias(EPI)) bj = bias[col];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1581,7 +1596,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6p_kernel(GemmP p) {
         const int row0 = m0 + wm + 32 * i + 8 * q + 4 * h;
         float* __restrict__ crow = C + (int64_t)row0 * p.ldc + col;
         float xa[4];
-        if constexpr (EPI == EPI_DELU) {
+        if constexpr (epi_aux(EPI)) {
           const float* __restrict__ xrow = ax + (int64_t)row0 * p.ld_aux + col;
 #pragma unroll
           for (int r = 0; r < 4; ++r) xa[r] = xrow[r * p.ld_aux];
@@ -1591,9 +1606,10 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6p_kernel(GemmP p) {
           float v = acc[i][j][4 * q + r];
           if (EPI == EPI_BIAS) v += bj;
           if (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
-          if constexpr (EPI == EPI_DELU) {
+          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
+          if constexpr (epi_aux(EPI)) {
             const float x = xa[r];
-            v = x > 0.f ? v : v * (x + 1.f);
+            v = EPI == EPI_DTANH ? v * (1.f - x * x) : (x > 0.f ? v : v * (x + 1.f));
           }
           crow[r * p.ldc] = v;
         }
@@ -1925,12 +1941,12 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6d_kernel(GemmP p) {
 
   float* __restrict__ C = p.C + g * p.gc;
   const float* __restrict__ bias = p.bias ? p.bias + g * p.gbias : nullptr;
-  const float* __restrict__ ax = EPI == EPI_DELU ? p.aux + g * p.gaux : nullptr;
+  const float* __restrict__ ax = epi_aux(EPI) ? p.aux + g * p.gaux : nullptr;
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int col = n0 + wn + 32 * j + li;
     float bj = 0.f;
-    if (EPI == EPI_BIAS || EPI == EPI_BIAS_ELU) bj = bias[col];
+    if (epi_bias(EPI)) bj = bias[col];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1938,7 +1954,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6d_kernel(GemmP p) {
         const int row0 = m0 + wm + 32 * i + 8 * q + 4 * h;
         float* __restrict__ crow = C + (int64_t)row0 * p.ldc + col;
         float xa[4];
-        if constexpr (EPI == EPI_DELU) {
+        if constexpr (epi_aux(EPI)) {
           const float* __restrict__ xrow = ax + (int64_t)row0 * p.ld_aux + col;
 #pragma unroll
           for (int r = 0; r < 4; ++r) xa[r] = xrow[r * p.ld_aux];
@@ -1948,9 +1964,10 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6d_kernel(GemmP p) {
           float v = acc[i][j][4 * q + r];
           if (EPI == EPI_BIAS) v += bj;
           if (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
-          if constexpr (EPI == EPI_DELU) {
+          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
+          if constexpr (epi_aux(EPI)) {
             const float x = xa[r];
-            v = x > 0.f ? v : v * (x + 1.f);
+            v = EPI == EPI_DTANH ? v * (1.f - x * x) : (x > 0.f ? v : v * (x + 1.f));
           }
           crow[r * p.ldc] = v;
         }
@@ -1970,9 +1987,11 @@ static void launch_x6d_l(const GemmP& p, int epi, int groups, hipStream_t st) {
   if (LAYOUT == GEMM_NT) {
     if (epi == EPI_STORE) LRL_X6D(EPI_STORE);
     else if (epi == EPI_BIAS) LRL_X6D(EPI_BIAS);
+    else if (epi == EPI_BIAS_TANH) LRL_X6D(EPI_BIAS_TANH);
     else LRL_X6D(EPI_BIAS_ELU);
   } else {
     if (epi == EPI_STORE) LRL_X6D(EPI_STORE);
+    else if (epi == EPI_DTANH) LRL_X6D(EPI_DTANH);
     else LRL_X6D(EPI_DELU);
   }
 #undef LRL_X6D
@@ -1996,8 +2015,8 @@ static bool x6d_enabled() { return x6d_mode() != 0; }
 static int try_x6d(const GemmP& p, int layout, int epi, int groups, int bm, int bn, hipStream_t st) {
   if (!x6d_enabled() || (layout != GEMM_NT && layout != GEMM_NN) || p.splits != 1) return 0;
   if (layout == GEMM_NT && x6d_mode() != 2) return 0;
-  if (layout == GEMM_NT && epi != EPI_STORE && epi != EPI_BIAS && epi != EPI_BIAS_ELU) return 0;
-  if (layout == GEMM_NN && epi != EPI_STORE && epi != EPI_DELU) return 0;
+  if (layout == GEMM_NT && epi != EPI_STORE && !epi_bias(epi)) return 0;
+  if (layout == GEMM_NN && epi != EPI_STORE && !epi_aux(epi)) return 0;
   if (p.M % bm || p.N % bn || p.K % 16 || p.K < 32 || p.avec != 4 || p.bvec != 4) return 0;
   if (layout == GEMM_NN && p.b_rows) return 0;
   const int key = (bm == 128 ? 2 : 0) | (bn == 128 ? 1 : 0) | (layout == GEMM_NN ? 4 : 0);
@@ -2068,7 +2087,7 @@ static int try_x6p(const GemmP& p, int layout, int epi, int groups, hipStream_t 
   if (!p.bpl || (__atomic_load_n(&g_path_off, __ATOMIC_RELAXED) & 1) || (layout != GEMM_NT && layout != GEMM_NN) ||
       p.splits != 1)
     return 0;
-  if (epi != EPI_STORE && epi != EPI_BIAS && epi != EPI_BIAS_ELU && epi != EPI_DELU) return 0;
+  if (epi != EPI_STORE && !epi_bias(epi) && !epi_aux(epi)) return 0;
   if (p.M % 64 || p.N % 128 || p.K % 16 || p.K < 32 || p.avec != 4 || p.bpl_ld != p.K) return 0;
   if ((reinterpret_cast<uintptr_t>(p.bpl) & 15) || p.gbp % 8 || p.bpl_ps % 8) return 0;
   // 128-row tiles when they give at least three per CU pair of workgroup slots, 64 otherwise
@@ -2090,6 +2109,8 @@ static int try_x6p(const GemmP& p, int layout, int epi, int groups, hipStream_t 
     case EPI_STORE: LRL_X6P_E(EPI_STORE); break;
     case EPI_BIAS: LRL_X6P_E(EPI_BIAS); break;
     case EPI_BIAS_ELU: LRL_X6P_E(EPI_BIAS_ELU); break;
+    case EPI_BIAS_TANH: LRL_X6P_E(EPI_BIAS_TANH); break;
+    case EPI_DTANH: LRL_X6P_E(EPI_DTANH); break;
     default: LRL_X6P_E(EPI_DELU); break;
   }
 #undef LRL_X6P_E
@@ -2156,12 +2177,14 @@ static int launch_bm(const GemmP& p, int layout, int epi, dim3 grid, hipStream_t
         case EPI_STORE: LRL_GEMM_LAUNCH(GEMM_NT, EPI_STORE); return 0;
         case EPI_BIAS: LRL_GEMM_LAUNCH(GEMM_NT, EPI_BIAS); return 0;
         case EPI_BIAS_ELU: LRL_GEMM_LAUNCH(GEMM_NT, EPI_BIAS_ELU); return 0;
+        case EPI_BIAS_TANH: LRL_GEMM_LAUNCH(GEMM_NT, EPI_BIAS_TANH); return 0;
       }
       break;
     case GEMM_NN:
       switch (epi) {
         case EPI_STORE: LRL_GEMM_LAUNCH(GEMM_NN, EPI_STORE); return 0;
         case EPI_DELU: LRL_GEMM_LAUNCH(GEMM_NN, EPI_DELU); return 0;
+        case EPI_DTANH: LRL_GEMM_LAUNCH(GEMM_NN, EPI_DTANH); return 0;
         case EPI_PARTIAL: LRL_GEMM_LAUNCH(GEMM_NN, EPI_PARTIAL); return 0;
       }
       break;
@@ -2226,6 +2249,10 @@ int gemm_last_path() { return g_last_path; }
 int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) {
   GemmP p = p0;
   if (p.M <= 0 || p.N <= 0 || p.K < 0 || groups <= 0) return LRL_E_INVALID;
+  // the tanh epilogues exist for the forward (NT) and backward-data (NN) products only: any other pairing is refused
+  // here, before a family's launcher could default it to an ELU instantiation
+  if ((epi == EPI_BIAS_TANH && layout != GEMM_NT) || (epi == EPI_DTANH && layout != GEMM_NN)) return LRL_E_INVALID;
+  if (epi == EPI_DTANH && !p.aux) return LRL_E_INVALID;
   if (p.splits <= 0) p.splits = 1;
   if (p.kps <= 0) p.kps = (p.K + p.splits - 1) / p.splits;
   p.kps = (p.kps + GBK - 1) / GBK * GBK;
@@ -2268,9 +2295,11 @@ int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) 
     if (layout == GEMM_NT) {
       if (epi == EPI_STORE) LRL_GLDS(GEMM_NT, EPI_STORE);
       else if (epi == EPI_BIAS) LRL_GLDS(GEMM_NT, EPI_BIAS);
+      else if (epi == EPI_BIAS_TANH) LRL_GLDS(GEMM_NT, EPI_BIAS_TANH);
       else LRL_GLDS(GEMM_NT, EPI_BIAS_ELU);
     } else {
       if (epi == EPI_STORE) LRL_GLDS(GEMM_NN, EPI_STORE);
+      else if (epi == EPI_DTANH) LRL_GLDS(GEMM_NN, EPI_DTANH);
       else LRL_GLDS(GEMM_NN, EPI_DELU);
     }
 #undef LRL_GLDS
@@ -2290,11 +2319,12 @@ int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) 
   const int kb128 = p.K / 128;
   if (layout != GEMM_TN && p.splits == 1 && p.N <= 32 && p.K % 128 == 0 && p.avec == 4 && p.M >= 256 &&
       (kb128 == 4 || kb128 == 8) &&  // (shorter k: the register-staged 128 x 32 tile is as fast)
-      (epi == EPI_STORE || epi == EPI_BIAS || epi == EPI_BIAS_ELU)) {
+      (epi == EPI_STORE || epi_bias(epi))) {
     int trc = LRL_E_INVALID;
     if (layout == GEMM_NT) {
       if (epi == EPI_STORE) trc = launch_thin<GEMM_NT, EPI_STORE>(p, groups, st);
       else if (epi == EPI_BIAS) trc = launch_thin<GEMM_NT, EPI_BIAS>(p, groups, st);
+      else if (epi == EPI_BIAS_TANH) trc = launch_thin<GEMM_NT, EPI_BIAS_TANH>(p, groups, st);
       else trc = launch_thin<GEMM_NT, EPI_BIAS_ELU>(p, groups, st);
     } else {
       if (epi == EPI_STORE) trc = launch_thin<GEMM_NN, EPI_STORE>(p, groups, st);

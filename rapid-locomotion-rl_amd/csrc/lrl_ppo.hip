@@ -101,6 +101,9 @@ __host__ __device__ constexpr int hp_std(int na) { return na * HEAD_W + na + HEA
 __host__ __device__ constexpr int hp_kl(int na) { return na * HEAD_W + na + HEAD_W + 1 + na; }
 __host__ __device__ constexpr int hp_len(int na) { return hp_kl(na) + 3; }  // kl, surrogate, value
 
+// NA: the action count (12: the quadrupeds' joints; 3: the navigation policy's commands), rows of per-action values
+// padded to NAP floats for the float4 reads; TANH: the bodies' activation (dH3 takes 1 - h^2 where ELU takes elu'(h))
+template <int NA, bool TANH>
 __global__ __launch_bounds__(HEAD_THREADS) void ppo_head_kernel(HeadArgs a) {
   // phases: (0) stage H3 / head weights and the minibatch rows' indices, then issue the gathered per-(row, action)
   // and per-row loads (old actions / mu / sigma, advantage, old log-prob, target value, return) so their latency
@@ -109,14 +112,14 @@ __global__ __launch_bounds__(HEAD_THREADS) void ppo_head_kernel(HeadArgs a) {
   // and the head weight-gradient partials.  Two global round trips in all (rows, then the gathered rows).
   // pitch 4 (mod 32) floats: the row-per-lane float4 reads of (1) hit distinct banks in every 8-lane group
   constexpr int HP = 2 * HEAD_W + 4;
-  constexpr int NA = HEAD_NA;
-  static_assert(NA % 4 == 0 && HEAD_W % 16 == 0, "float4 rows");
+  constexpr int NAP = (NA + 3) / 4 * 4;
+  static_assert(NA <= 16 && HEAD_W % 16 == 0, "float4 rows");  // (t < NA, t == 16 and t >= 32 share the last phase)
   constexpr int NG = (HEAD_ROWS * NA + HEAD_THREADS - 1) / HEAD_THREADS;  // gathered (row, action) items per thread
   __shared__ __attribute__((aligned(16))) float H[HEAD_ROWS][HP];
   __shared__ __attribute__((aligned(16))) float W4[NA + 1][HEAD_W];
   __shared__ float MU[HEAD_ROWS][NA + 1];   // mu_j, then d = a_j - mu_j
   __shared__ float VP[HEAD_ROWS][8];
-  __shared__ __attribute__((aligned(16))) float LP[HEAD_ROWS][NA];  // log-prob term, then d loss / d mu
+  __shared__ __attribute__((aligned(16))) float LP[HEAD_ROWS][NAP];  // log-prob term, then d loss / d mu
   __shared__ float KT[HEAD_ROWS][NA];       // KL term, then d loss / d std
   __shared__ float DR[HEAD_ROWS][2];        // d loss / d logp, d loss / d v
   __shared__ float SC[HEAD_ROWS][3];        // kl, surrogate, value loss per row
@@ -301,9 +304,9 @@ __global__ __launch_bounds__(HEAD_THREADS) void ppo_head_kernel(HeadArgs a) {
 #pragma unroll 2
       for (int r = 0; r < nrows; ++r) {
         const float h = H[r][k];
-        float dmr[NA];  // (row r's d loss / d mu: NA / 4 broadcast float4 reads)
+        float dmr[NAP];  // (row r's d loss / d mu: NAP / 4 broadcast float4 reads; columns past NA are not used)
 #pragma unroll
-        for (int j4 = 0; j4 < NA / 4; ++j4) {
+        for (int j4 = 0; j4 < NAP / 4; ++j4) {
           const float4 v = reinterpret_cast<const float4*>(&LP[r][0])[j4];
           dmr[4 * j4] = v.x; dmr[4 * j4 + 1] = v.y; dmr[4 * j4 + 2] = v.z; dmr[4 * j4 + 3] = v.w;
         }
@@ -314,7 +317,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void ppo_head_kernel(HeadArgs a) {
           s = fmaf(dm, wk[j], s);
           accw[j] = fmaf(dm, h, accw[j]);
         }
-        a.dh3[(int64_t)(r0 + r) * (2 * HEAD_W) + k] = s * delu(h);
+        a.dh3[(int64_t)(r0 + r) * (2 * HEAD_W) + k] = s * (TANH ? 1.f - h * h : delu(h));
       }
 #pragma unroll
       for (int j = 0; j < NA; ++j) P[hp_w4a(NA) + j * HEAD_W + k] = accw[j];
@@ -326,7 +329,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void ppo_head_kernel(HeadArgs a) {
         const float h = H[r][k];
         const float d = DR[r][1];
         accc = fmaf(d, h, accc);
-        a.dh3[(int64_t)(r0 + r) * (2 * HEAD_W) + k] = (d * wk) * delu(h);
+        a.dh3[(int64_t)(r0 + r) * (2 * HEAD_W) + k] = (d * wk) * (TANH ? 1.f - h * h : delu(h));
       }
       P[hp_w4c(NA) + kk] = accc;
     }
@@ -499,7 +502,8 @@ __global__ __launch_bounds__(HEAD_THREADS) void act_head_kernel(ActHeadArgs a) {
   if (a.do_store) {  // obs / priv / history rows of this tile into storage row `store_row`
     const int64_t b = so + r0;
     copy_rows(a.obs + (int64_t)r0 * a.no, a.no, a.store.obs + b * a.no, a.no, nrows, a.no, t);
-    copy_rows(a.priv + (int64_t)r0 * a.np, a.np, a.store.priv + b * a.np, a.np, nrows, a.np, t);
+    if (a.priv)  // (NULL: a plain net acting without privileged observations)
+      copy_rows(a.priv + (int64_t)r0 * a.np, a.np, a.store.priv + b * a.np, a.np, nrows, a.np, t);
     if (a.hist && a.store.hist) {
       const int hd = a.store.hist_dim, ld = a.store.hist_ld > hd ? a.store.hist_ld : hd;
       copy_rows(a.hist + (int64_t)r0 * hd, hd, a.store.hist + b * ld, ld, nrows, hd, t);
@@ -1123,6 +1127,7 @@ static int64_t plane_area_elems(const lrl_ppo_net& n) {
 // X = [obs | latent] row pitch: 64 for the blind policies (42 + 18), else rounded up to 16 floats (a height-scan
 // policy: 235 + 18 -> 256).  Columns nx..XS-1 are zero.
 static int xs_of(const lrl_ppo_net& n) {
+  if (n.plain) return (n.num_obs + 15) / 16 * 16;  // X = [obs | 0-pad] (14 -> 16)
   const int nx = n.num_obs + n.latent;
   return nx <= 64 ? 64 : (nx + 15) / 16 * 16;
 }
@@ -1137,7 +1142,7 @@ static int64_t tn_part_floats(int M, int N, int K, int groups) {
 }
 
 static Plan make_plan(const lrl_ppo_net& n, int B, char* base) {
-  Plan p;
+  Plan p{};
   p.B = B;
   int64_t off = 0;
   auto take = [&](int64_t floats) {
@@ -1146,6 +1151,22 @@ static Plan make_plan(const lrl_ppo_net& n, int B, char* base) {
     return r;
   };
   const int64_t Bl = B;
+  if (n.plain) {  // actor / critic bodies over the observations alone: no encoder, latent or adaptation buffers
+    p.xa = take(Bl * xs_of(n));
+    p.h1 = take(Bl * 2 * n.ac_h0);
+    p.h2 = take(Bl * 2 * n.ac_h1);
+    p.h3 = take(Bl * 2 * n.ac_h2);
+    p.dh3 = take(Bl * 2 * n.ac_h2);
+    p.dh2 = take(Bl * 2 * n.ac_h1);
+    p.dh1 = take(Bl * 2 * n.ac_h0);
+    const int hbp = (B + HEAD_ROWS - 1) / HEAD_ROWS;
+    // (64 * 8 floats of slack: the head's slice and each product's cursor are rounded up to 64 floats)
+    p.part_floats = tn_part_floats(n.ac_h2, n.ac_h1, B, 2) + tn_part_floats(n.ac_h1, n.ac_h0, B, 2) +
+                    tn_part_floats(2 * n.ac_h0, n.num_obs, B, 1) + (int64_t)hbp * hp_len(n.num_actions) + 64 * 8;
+    p.part = take(p.part_floats);
+    p.bytes = off;
+    return p;
+  }
   p.xa = take(Bl * xs_of(n));
   p.he1 = take(Bl * n.enc_h0);
   p.he2 = take(Bl * n.enc_h1);
@@ -1181,6 +1202,20 @@ static Plan make_plan(const lrl_ppo_net& n, int B, char* base) {
 static int check_net(const lrl_ppo_net* n) {
   if (!n) return lrl_set_error(LRL_E_INVALID, "lrl_ppo: null net");
   if (n->ac_h2 != HEAD_W) return lrl_set_error(LRL_E_INVALID, "lrl_ppo: last actor/critic hidden width must be 128");
+  if ((n->activation != 0 && n->activation != 1) || (n->plain != 0 && n->plain != 1))
+    return lrl_set_error(LRL_E_INVALID, "lrl_ppo: activation / plain must be 0 or 1");
+  if (n->plain) {  // plain MLP bodies over the observations (the navigation policy): tanh, 3 or 12 actions
+    if (n->activation != 1) return lrl_set_error(LRL_E_INVALID, "lrl_ppo: a plain net must use tanh (activation = 1)");
+    if (n->num_actions != 3 && n->num_actions != HEAD_NA)
+      return lrl_set_error(LRL_E_INVALID, "lrl_ppo: a plain net's num_actions must be 3 or 12");
+    if (n->latent || n->enc_h0 || n->enc_h1 || n->ad_h0 || n->ad_h1 || n->adapt_begin != n->adapt_end)
+      return lrl_set_error(LRL_E_INVALID, "lrl_ppo: a plain net has no encoder, latent or adaptation module");
+    if (n->num_obs <= 0 || n->ac_h0 <= 0 || n->ac_h1 <= 0)
+      return lrl_set_error(LRL_E_INVALID, "lrl_ppo: a plain net needs num_obs, ac_h0, ac_h1 > 0");
+    return 0;
+  }
+  if (n->activation != 0)
+    return lrl_set_error(LRL_E_INVALID, "lrl_ppo: tanh is implemented for plain nets only (activation = 1 needs plain = 1)");
   if (n->num_actions != HEAD_NA) return lrl_set_error(LRL_E_INVALID, "lrl_ppo: num_actions must be 12");
   if (n->latent > MAX_LAT || n->ad_h1 > MAX_LAT) return lrl_set_error(LRL_E_INVALID, "lrl_ppo: latent/adaptation widths > 32");
   return 0;
@@ -1219,6 +1254,7 @@ struct G {
   float* part_end;  // end of the partial area: a product that would not fit is refused before launch
   int rc = 0;
   const PlaneJob* pl = nullptr;  // pre-split B of the next nt / nn product (consumed by it)
+  bool tanh_act = false;         // the activation epilogues: tanh / 1 - y^2 instead of ELU / elu'
   G& with(const PlaneJob& j) {
     pl = &j;
     return *this;
@@ -1236,7 +1272,7 @@ struct G {
     p.M = M; p.N = N; p.K = K; p.splits = 1;
     p.ga = ga; p.gb = gw; p.gc = gc; p.gbias = gbias;
     take_planes(p);
-    rc = gemm_launch(p, GEMM_NT, elu ? EPI_BIAS_ELU : EPI_BIAS, groups, st);
+    rc = gemm_launch(p, GEMM_NT, elu ? (tanh_act ? EPI_BIAS_TANH : EPI_BIAS_ELU) : EPI_BIAS, groups, st);
   }
   // dX = dY W (* elu'(aux) if aux)
   void nn(const float* dY, int64_t ldy, const float* W, int64_t ldw, float* dX, int64_t ldx, const float* aux,
@@ -1248,7 +1284,7 @@ struct G {
     p.M = M; p.N = N; p.K = K; p.splits = 1;
     p.ga = gy; p.gb = gw; p.gc = gx; p.gaux = gaux;
     take_planes(p);
-    rc = gemm_launch(p, GEMM_NN, aux ? EPI_DELU : EPI_STORE, groups, st);
+    rc = gemm_launch(p, GEMM_NN, aux ? (tanh_act ? EPI_DTANH : EPI_DELU) : EPI_STORE, groups, st);
   }
   // partial dW[o][i] = sum_b dY[b][o] X[rows(b)][i]; returns the segments (weights then biases)
   void tn(const float* dY, int64_t ldy, const float* X, int64_t ldx, const int64_t* rows, int M, int N, int K,
@@ -1361,6 +1397,15 @@ static ActPlan make_act_plan(const lrl_ppo_net& n, int rows, char* base) {
     return r;
   };
   const int64_t R = rows;
+  if (n.plain) {  // X = [obs | 0] and the three hidden layers
+    p = ActPlan{};
+    p.xa = take(R * xs_of(n));
+    p.h1 = take(R * 2 * n.ac_h0);
+    p.h2 = take(R * 2 * n.ac_h1);
+    p.h3 = take(R * 2 * n.ac_h2);
+    p.bytes = off;
+    return p;
+  }
   p.xa = take(R * xs_of(n));
   p.he1 = take(R * n.enc_h0);
   p.he2 = take(R * n.enc_h1);
@@ -1438,13 +1483,43 @@ extern "C" int32_t lrl_ppo_act(const lrl_ppo_net* net, const float* params, cons
                                int64_t row_offset, float* actions, float* mu, float* values, float* logp, const lrl_rollout_store* store,
                                int32_t store_row, void* workspace, void* stream) {
   if (int rc = check_net(net)) return rc;
-  if (!params || !obs || !priv || !actions || !workspace || n <= 0)
+  if (!params || !obs || (!priv && !net->plain) || !actions || !workspace || n <= 0)
     return lrl_set_error(LRL_E_INVALID, "lrl_ppo_act: null argument or n <= 0");
-  if (store && (!store->obs || !store->priv || !store->actions || !store->values || !store->logp || !store->mu ||
-                !store->sigma || store->hist_dim < 0 || (store->hist_ld != 0 && store->hist_ld < store->hist_dim)))
+  if (store && (!store->obs || (!store->priv && priv) || !store->actions || !store->values || !store->logp ||
+                !store->mu || !store->sigma || store->hist_dim < 0 ||
+                (store->hist_ld != 0 && store->hist_ld < store->hist_dim)))
     return lrl_set_error(LRL_E_INVALID, "lrl_ppo_act: incomplete rollout store");
   const lrl_ppo_net& nt = *net;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (nt.plain) {
+    // plain tanh bodies over the observations alone (priv / hist may be NULL: they are only copied into the storage
+    // row when given): X = [obs | 0], three grouped [actor; critic] layers, the head.  The one-launch fused act is
+    // built around the presets' encoder and widths and is not taken here.
+    ActPlan P = make_act_plan(nt, n, static_cast<char*>(workspace));
+    G g{st, nullptr};
+    g.tanh_act = true;
+    const float* w = params;
+    const int no = nt.num_obs, XS = xs_of(nt);
+    hipLaunchKernelGGL(ppo_prep_kernel, dim3(prep_blocks(n, XS)), dim3(256), 0, st, obs, (const int64_t*)nullptr, n, no,
+                       XS, P.xa);
+    // (k runs over X's zero padding: see lrl_ppo_forward_backward)
+    g.nt(P.xa, XS, nullptr, w + nt.w1, no, P.h1, 2 * nt.ac_h0, w + nt.b1, n, 2 * nt.ac_h0, XS, true);
+    g.nt(P.h1, 2 * nt.ac_h0, nullptr, w + nt.w2, nt.ac_h0, P.h2, 2 * nt.ac_h1, w + nt.b2, n, nt.ac_h1, nt.ac_h0, true, 2,
+         nt.ac_h0, (int64_t)nt.ac_h1 * nt.ac_h0, nt.ac_h1, nt.ac_h1);
+    g.nt(P.h2, 2 * nt.ac_h1, nullptr, w + nt.w3, nt.ac_h1, P.h3, 2 * nt.ac_h2, w + nt.b3, n, nt.ac_h2, nt.ac_h1, true, 2,
+         nt.ac_h1, (int64_t)nt.ac_h2 * nt.ac_h1, nt.ac_h2, nt.ac_h2);
+    if (g.rc) return lrl_set_error(g.rc, "lrl_ppo_act: GEMM launch failed");
+    ActHeadArgs ah{};
+    ah.h3 = P.h3; ah.w4a = w + nt.w4a; ah.b4a = w + nt.b4a; ah.w4c = w + nt.w4c; ah.b4c = w + nt.b4c;
+    ah.stdv = w + nt.std_off; ah.obs = obs; ah.priv = priv; ah.hist = hist; ah.eps = eps;
+    ah.n = n; ah.na = nt.num_actions; ah.no = no; ah.np = nt.num_priv; ah.seed = seed; ah.counter = counter;
+    ah.row_offset = row_offset;
+    ah.actions = actions; ah.mu = mu; ah.values = values; ah.logp = logp;
+    if (store) ah.store = *store;
+    ah.store_row = store_row; ah.do_store = store ? 1 : 0;
+    hipLaunchKernelGGL(act_head_kernel, dim3((n + ACT_ROWS - 1) / ACT_ROWS), dim3(HEAD_THREADS), 0, st, ah);
+    return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_ppo_act: launch failed");
+  }
   if (fused_act_fits(nt)) {  // one launch: act_fused_kernel
     static const bool ok = [] {
       auto set = [](const void* f) {
@@ -1553,7 +1628,7 @@ static StudentPlan make_student_plan(const lrl_ppo_net& n, int rows, char* base)
 }
 
 extern "C" int64_t lrl_ppo_act_student_workspace_bytes(const lrl_ppo_net* net, int32_t n) {
-  if (check_net(net) || n <= 0) return -1;
+  if (check_net(net) || net->plain || n <= 0) return -1;
   return make_student_plan(*net, n, nullptr).bytes;
 }
 
@@ -1561,6 +1636,7 @@ extern "C" int32_t lrl_ppo_act_student(const lrl_ppo_net* net, const float* para
                                        const float* hist, int32_t hist_ld, int32_t n, float* mean, float* latent,
                                        void* workspace, void* stream) {
   if (int rc = check_net(net)) return rc;
+  if (net->plain) return lrl_set_error(LRL_E_INVALID, "lrl_ppo_act_student: a plain net has no adaptation module");
   if (!params || !obs || !hist || !mean || !workspace || n <= 0)
     return lrl_set_error(LRL_E_INVALID, "lrl_ppo_act_student: null argument or n <= 0");
   const lrl_ppo_net& nt = *net;
@@ -1615,6 +1691,53 @@ extern "C" int32_t lrl_ppo_forward_backward(const lrl_ppo_net* net, const float*
   G g{st, P.part + P.part_floats};
   const float* w = params;
   const int nx = n.num_obs + n.latent, XS = xs_of(n);
+  if (n.plain) {
+    // plain tanh bodies (the navigation policy): obs rows gathered at pitch XS = round16(num_obs), three grouped
+    // [actor; critic] layers, the head, the backward-data chain, three weight gradients — one stream, fp32 B operands
+    g.tanh_act = true;
+    const int h0 = n.ac_h0, h1 = n.ac_h1, h2 = n.ac_h2, na = n.num_actions;
+    hipLaunchKernelGGL(ppo_prep_kernel, dim3(prep_blocks(B, XS)), dim3(256), 0, st, bt->obs, bt->rows, B, n.num_obs, XS,
+                       P.xa);
+    // (k runs over X's zero columns nx..XS-1 against the next row's first weights / the biases after the last row)
+    g.nt(P.xa, XS, nullptr, w + n.w1, nx, P.h1, 2 * h0, w + n.b1, B, 2 * h0, XS, true);
+    g.nt(P.h1, 2 * h0, nullptr, w + n.w2, h0, P.h2, 2 * h1, w + n.b2, B, h1, h0, true, 2, h0, (int64_t)h1 * h0, h1, h1);
+    g.nt(P.h2, 2 * h1, nullptr, w + n.w3, h1, P.h3, 2 * h2, w + n.b3, B, h2, h1, true, 2, h1, (int64_t)h2 * h1, h2, h2);
+    if (g.rc) return lrl_set_error(g.rc, "lrl_ppo_forward_backward: forward GEMM launch failed");
+    SegList L{};
+    float* part = P.part;
+    const int hb = (B + HEAD_ROWS - 1) / HEAD_ROWS;
+    HeadArgs ha{};
+    ha.h3 = P.h3; ha.dh3 = P.dh3;
+    ha.w4a = w + n.w4a; ha.b4a = w + n.b4a; ha.w4c = w + n.w4c; ha.b4c = w + n.b4c; ha.stdv = w + n.std_off;
+    ha.actions = bt->actions; ha.old_mu = bt->mu; ha.old_sigma = bt->sigma; ha.tv = bt->values; ha.ret = bt->returns;
+    ha.adv = bt->adv; ha.old_logp = bt->logp; ha.rows = bt->rows;
+    ha.B = B; ha.na = na; ha.clip = hp->clip_param; ha.ent_coef = hp->entropy_coef; ha.vcoef = hp->value_loss_coef;
+    ha.clipped_value = hp->use_clipped_value_loss;
+    ha.part = part; ha.part_len = hp_len(na);
+    if (na == 3) hipLaunchKernelGGL((ppo_head_kernel<3, true>), dim3(hb), dim3(HEAD_THREADS), 0, st, ha);
+    else hipLaunchKernelGGL((ppo_head_kernel<HEAD_NA, true>), dim3(hb), dim3(HEAD_THREADS), 0, st, ha);
+    {
+      const int64_t pl = hp_len(na);
+      const float invB = 1.f / (float)B;
+      L.s[L.n++] = Seg{part + hp_w4a(na), grads + n.w4a, (int64_t)na * HEAD_W, pl, hb, 1.f};
+      L.s[L.n++] = Seg{part + hp_b4a(na), grads + n.b4a, na, pl, hb, 1.f};
+      L.s[L.n++] = Seg{part + hp_w4c(na), grads + n.w4c, HEAD_W, pl, hb, 1.f};
+      L.s[L.n++] = Seg{part + hp_b4c(na), grads + n.b4c, 1, pl, hb, 1.f};
+      L.s[L.n++] = Seg{part + hp_std(na), grads + n.std_off, na, pl, hb, 1.f};
+      L.s[L.n++] = Seg{part + hp_kl(na), grads + n.kl_slot, 1, pl, hb, invB};
+      L.s[L.n++] = Seg{part + hp_kl(na) + 1, &ctrl->mb[1], 1, pl, hb, invB};
+      L.s[L.n++] = Seg{part + hp_kl(na) + 2, &ctrl->mb[0], 1, pl, hb, invB};
+      part += ((hb * pl + 63) / 64) * 64;
+    }
+    g.nn(P.dh3, 2 * h2, w + n.w3, h1, P.dh2, 2 * h1, P.h2, 2 * h1, B, h1, h2, 2, h2, (int64_t)h2 * h1, h1, h1);
+    g.nn(P.dh2, 2 * h1, w + n.w2, h0, P.dh1, 2 * h0, P.h1, 2 * h0, B, h0, h1, 2, h1, (int64_t)h1 * h0, h0, h0);
+    g.tn(P.dh3, 2 * h2, P.h2, 2 * h1, nullptr, h2, h1, B, 2, h2, h1, part, grads + n.w3, grads + n.b3, L);
+    g.tn(P.dh2, 2 * h1, P.h1, 2 * h0, nullptr, h1, h0, B, 2, h1, h0, part, grads + n.w2, grads + n.b2, L);
+    g.tn(P.dh1, 2 * h0, P.xa, XS, nullptr, 2 * h0, nx, B, 1, 0, 0, part, grads + n.w1, grads + n.b1, L);
+    if (g.rc) return lrl_set_error(g.rc, "lrl_ppo_forward_backward: backward GEMM launch failed");
+    launch_seg(L, st);
+    return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_ppo_forward_backward: launch failed");
+  }
   // ---- forward ----
   PlaneJob pj[PL_MAIN];
   main_plane_jobs(n, w, P.wpl, pj);
@@ -1651,7 +1774,7 @@ extern "C" int32_t lrl_ppo_forward_backward(const lrl_ppo_net* net, const float*
   ha.B = B; ha.na = na; ha.clip = hp->clip_param; ha.ent_coef = hp->entropy_coef; ha.vcoef = hp->value_loss_coef;
   ha.clipped_value = hp->use_clipped_value_loss;
   ha.part = part; ha.part_len = hp_len(na);
-  hipLaunchKernelGGL(ppo_head_kernel, dim3(hb), dim3(HEAD_THREADS), 0, st, ha);
+  hipLaunchKernelGGL((ppo_head_kernel<HEAD_NA, false>), dim3(hb), dim3(HEAD_THREADS), 0, st, ha);
   {
     const int64_t pl = hp_len(na);
     const float invB = 1.f / (float)B;
@@ -1729,6 +1852,8 @@ extern "C" int32_t lrl_ppo_adaptation_forward_backward(const lrl_ppo_net* net, c
                                                        const float* enc_params, float* grads, const lrl_ppo_batch* bt,
                                                        void* workspace, lrl_ppo_ctrl* ctrl, void* stream) {
   if (int rc = check_net(net)) return rc;
+  if (net->plain)
+    return lrl_set_error(LRL_E_INVALID, "lrl_ppo_adaptation_forward_backward: a plain net has no adaptation module");
   if (!bt || !params || !grads || !workspace || !ctrl || bt->batch <= 0)
     return lrl_set_error(LRL_E_INVALID, "lrl_ppo_adaptation_forward_backward: null argument");
   const lrl_ppo_net& n = *net;
@@ -1795,6 +1920,7 @@ extern "C" int32_t lrl_ppo_adaptation_step(const lrl_ppo_net* net, float* params
                                            float* exp_avg_sq, int64_t step, double lr, float grad_scale,
                                            const lrl_ppo_hparams* hp, lrl_ppo_ctrl* ctrl, void* stream) {
   if (int rc = check_net(net)) return rc;
+  if (net->plain) return lrl_set_error(LRL_E_INVALID, "lrl_ppo_adaptation_step: a plain net has no adaptation module");
   if (!params || !grads || !exp_avg || !exp_avg_sq || !hp || step < 1)
     return lrl_set_error(LRL_E_INVALID, "lrl_ppo_adaptation_step: bad argument");
   const lrl_ppo_net& n = *net;
@@ -1819,6 +1945,9 @@ extern "C" int32_t lrl_gemm_f32(int32_t layout, int32_t epi, int32_t M, int32_t 
   GemmP p{};
   p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc; p.bias = bias; p.aux = aux; p.ld_aux = ld_aux;
   p.M = M; p.N = N; p.K = K; p.splits = 1;
+  if ((epi == EPI_BIAS_TANH && (layout & 0xff) != GEMM_NT) || (epi == EPI_DTANH && (layout & 0xff) != GEMM_NN))
+    return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32: epi 5 is an NT epilogue, epi 6 an NN one");
+  if (epi == EPI_DTANH && !aux) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32: epi 6 needs aux");
   if (layout == GEMM_TN) {
     // split-k into the workspace, then reduce into C (C must be [M][N] contiguous: ldc == N)
     if (ldc != N) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32: TN needs ldc == N");

@@ -98,7 +98,8 @@ class LrlPpoNet(C.Structure):
                                     "ac_h0", "ac_h1", "ac_h2", "ad_h0", "ad_h1")] + \
                [(k, i64) for k in ("w1", "b1", "w2", "b2", "w3", "b3", "w4a", "b4a", "w4c", "b4c", "e1w", "e1b", "e2w",
                                     "e2b", "e3w", "e3b", "d1w", "d1b", "d2w", "d2b", "d3w", "d3b", "std_off",
-                                    "main_begin", "main_end", "adapt_begin", "adapt_end", "kl_slot", "total")]
+                                    "main_begin", "main_end", "adapt_begin", "adapt_end", "kl_slot", "total")] + \
+               [("activation", i32), ("plain", i32)]  # 0 = ELU / 1 = tanh; 1 = plain MLP over obs (lrl/hlp)
 
 
 class LrlPpoBatch(C.Structure):

@@ -212,7 +212,8 @@ class ActorCritic(nn.Module):
         rank's env_offset), so a sharded rollout samples what one process holding every env would."""
         n = obs.shape[0]
         dev = obs.device
-        assert obs.is_contiguous() and priv.is_contiguous() and obs.dtype == torch.float32
+        # (priv None: a plain net — lrl.hlp — acts on the observations alone)
+        assert obs.is_contiguous() and (priv is None or priv.is_contiguous()) and obs.dtype == torch.float32
         net = self.flatten_parameters()
         ws = getattr(self, "_act_ws", None)
         if ws is None or ws[0] != n or ws[1].device != dev:

@@ -80,16 +80,18 @@ def _all_reduce_(t):
 
 class PPO:
     actor_critic: ActorCritic
+    args = PPO_Args  # the argument class the methods read (lrl.hlp's PPO carries its own)
+    storage_class = RolloutStorage
 
     def __init__(self, actor_critic, device="cpu", fused=None, seed=0):
         self.device = device
         self.actor_critic = actor_critic.to(device)
         self.storage = None
-        self.optimizer = torch.optim.Adam(self.actor_critic.parameters(), lr=PPO_Args.learning_rate)
+        self.optimizer = torch.optim.Adam(self.actor_critic.parameters(), lr=self.args.learning_rate)
         self.adaptation_module_optimizer = torch.optim.Adam(self.actor_critic.parameters(),
-                                                            lr=PPO_Args.adaptation_module_learning_rate)
+                                                            lr=self.args.adaptation_module_learning_rate)
         self.transition = RolloutStorage.Transition()
-        self._lr = float(PPO_Args.learning_rate)
+        self._lr = float(self.args.learning_rate)
         self.async_losses = False
         self._lr_dev = None  # the native update's ctrl tensor while its learning rate is newer than self._lr
         self.fused = (torch.device(device).type == "cuda") if fused is None else fused
@@ -109,8 +111,8 @@ class PPO:
 
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, privileged_obs_shape, obs_history_shape,
                      action_shape):
-        self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, privileged_obs_shape,
-                                      obs_history_shape, action_shape, self.device)
+        self.storage = self.storage_class(num_envs, num_transitions_per_env, actor_obs_shape, privileged_obs_shape,
+                                          obs_history_shape, action_shape, self.device)
         self._store = self.storage.store_desc() if self.fused else None
 
     def test_mode(self):
@@ -152,7 +154,7 @@ class PPO:
         t.dones = dones
         t.env_bins = infos["env_bins"]
         if "time_outs" in infos:  # bootstrapping on time outs (ppo.py:81-83)
-            t.rewards += PPO_Args.gamma * torch.squeeze(t.values * infos["time_outs"].unsqueeze(1).to(self.device), 1)
+            t.rewards += self.args.gamma * torch.squeeze(t.values * infos["time_outs"].unsqueeze(1).to(self.device), 1)
         self.storage.add_transitions(t, fused=self.fused)
         t.clear()
         self.actor_critic.reset(dones)
@@ -174,7 +176,7 @@ class PPO:
         p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
         stream = _abi.stream_of(rewards.device)
         _abi.check(_abi.lib().lrl_ppo_store_step(p(rewards), p(dones), p(bins), p(t.values if tout is not None else None),
-                                                 p(tout), C.c_float(PPO_Args.gamma), C.c_int32(n), p(s.rewards[i]),
+                                                 p(tout), C.c_float(self.args.gamma), C.c_int32(n), p(s.rewards[i]),
                                                  p(s.dones[i]), p(s.env_bins[i]), stream))
         s.step += 1
         return True
@@ -189,7 +191,7 @@ class PPO:
         reduce = None
         if _collective():
             reduce = _all_reduce_
-        self.storage.compute_returns(last_values, PPO_Args.gamma, PPO_Args.lam, reduce_stats=reduce)
+        self.storage.compute_returns(last_values, self.args.gamma, self.args.lam, reduce_stats=reduce)
 
     def _allreduce_grads(self, params):
         grads = [p.grad for p in params if p.grad is not None]
@@ -216,11 +218,11 @@ class PPO:
                       ctrl=torch.zeros(_abi.PPO_CTRL_BYTES // 8, dtype=torch.float64, device=dev),
                       steps=[0, 0], ws=None, ws_batch=0)
             hp = _abi.LrlPpoHparams()
-            _abi.fill(hp, clip_param=PPO_Args.clip_param, entropy_coef=PPO_Args.entropy_coef,
-                      value_loss_coef=PPO_Args.value_loss_coef, max_grad_norm=PPO_Args.max_grad_norm,
-                      desired_kl=PPO_Args.desired_kl if PPO_Args.desired_kl is not None else 0.0,
-                      use_clipped_value_loss=int(PPO_Args.use_clipped_value_loss),
-                      adaptive_schedule=int(PPO_Args.desired_kl is not None and PPO_Args.schedule == "adaptive"),
+            _abi.fill(hp, clip_param=self.args.clip_param, entropy_coef=self.args.entropy_coef,
+                      value_loss_coef=self.args.value_loss_coef, max_grad_norm=self.args.max_grad_norm,
+                      desired_kl=self.args.desired_kl if self.args.desired_kl is not None else 0.0,
+                      use_clipped_value_loss=int(self.args.use_clipped_value_loss),
+                      adaptive_schedule=int(self.args.desired_kl is not None and self.args.schedule == "adaptive"),
                       beta1=0.9, beta2=0.999, eps=1e-8)
             st["hp"] = hp
             self._native = st
@@ -230,7 +232,8 @@ class PPO:
                 raise RuntimeError("lrl_ppo_workspace_bytes rejected the network")
             st["ws"] = torch.empty(nbytes, dtype=torch.uint8, device=ac._flat.device)
             # the adaptation phases run on their own stream with their own workspace (see _update_native)
-            st["ws_b"] = torch.empty(nbytes, dtype=torch.uint8, device=ac._flat.device)
+            # (a plain net has no adaptation phases: no second workspace)
+            st["ws_b"] = st["ws"] if net.plain else torch.empty(nbytes, dtype=torch.uint8, device=ac._flat.device)
             st["ws_batch"] = batch
         return st
 
@@ -253,7 +256,7 @@ class PPO:
     def _update_native(self, sync=True):
         s = self.storage
         T, N = s.num_transitions_per_env, s.num_envs
-        nmb = PPO_Args.num_mini_batches
+        nmb = self.args.num_mini_batches
         mb = (T * N) // nmb
         st = self._native_state(mb)
         net, hp = st["net"], st["hp"]
@@ -313,7 +316,7 @@ class PPO:
             st["read_done_ev"] = [torch.cuda.Event() for _ in range(_SNAPSHOTS)]
         read_done = [None] * _SNAPSHOTS
         k = 0
-        for epoch in range(PPO_Args.num_learning_epochs):
+        for epoch in range(self.args.num_learning_epochs):
             for i in range(nmb):
                 rows = indices[i * mb:(i + 1) * mb]
                 batch.rows = rows.data_ptr()
@@ -336,7 +339,8 @@ class PPO:
                     enc = ptr(snap)
                     sb.wait_stream(cur)
                 batch_b.rows = rows.data_ptr()
-                for _ in range(PPO_Args.num_adaptation_module_substeps):
+                # (a plain net — lrl.hlp's policy, which also turns overlap_adaptation off — has no adaptation phases)
+                for _ in range(0 if net.plain else self.args.num_adaptation_module_substeps):
                     _abi.check(L.lrl_ppo_adaptation_forward_backward(C.byref(net), ptr(params), enc, ptr(grads),
                                                                      C.byref(batch_b), ptr(ws_b), ptr(ctrl), stream_b))
                     if coll:
@@ -345,7 +349,7 @@ class PPO:
                     st["steps"][1] += 1
                     _abi.check(L.lrl_ppo_adaptation_step(C.byref(net), ptr(params), ptr(grads), ptr(m), ptr(v),
                                                          C.c_int64(st["steps"][1]),
-                                                         C.c_double(PPO_Args.adaptation_module_learning_rate),
+                                                         C.c_double(self.args.adaptation_module_learning_rate),
                                                          C.c_float(scale), C.byref(hp), ptr(ctrl), stream_b))
                 if sb is not cur:
                     ev = st["read_done_ev"][k % _SNAPSHOTS]
@@ -355,14 +359,14 @@ class PPO:
         if sb is not cur:
             cur.wait_stream(sb)
             indices.record_stream(sb)
-        num_updates = PPO_Args.num_learning_epochs * nmb
+        num_updates = self.args.num_learning_epochs * nmb
         if self.record_lr:
             self.lr_trace = torch.stack(trace).tolist()
         self._lr_dev = ctrl  # the learning rate stays on the device (read lazily by .learning_rate)
         self.storage.clear()
         # the divisors are a cached device tensor: a torch.tensor(list, device=...) here is a pageable host -> device
         # copy, which waits for the whole update to finish and so keeps the host from enqueuing the next rollout
-        den_key = (num_updates, PPO_Args.num_adaptation_module_substeps)
+        den_key = (num_updates, self.args.num_adaptation_module_substeps)
         if st.get("loss_den_key") != den_key:
             st["loss_den"] = torch.tensor([num_updates, num_updates, num_updates * den_key[1]], dtype=ctrl.dtype,
                                           device=ctrl.device)
@@ -372,6 +376,23 @@ class PPO:
             return tuple(losses.unbind(0))
         vsum, ssum, asum = losses.tolist()
         return vsum, ssum, asum
+
+    def _adaptation_substeps(self, hist_b, priv_b, params):
+        """The adaptation-module regression of one minibatch (ppo.py:157-171, torch form): the summed MSE losses."""
+        ac = self.actor_critic
+        total = torch.zeros((), device=self.device)
+        for _ in range(self.args.num_adaptation_module_substeps):
+            adaptation_pred = ac.adaptation_module(hist_b)
+            with torch.no_grad():
+                adaptation_target = ac.env_factor_encoder(priv_b)
+            adaptation_loss = F.mse_loss(adaptation_pred, adaptation_target)
+            self.adaptation_module_optimizer.zero_grad()
+            adaptation_loss.backward()
+            if self.grad_allreduce:
+                self._allreduce_grads(params)
+            self.adaptation_module_optimizer.step()
+            total += adaptation_loss.detach()
+        return total
 
     def update(self):
         """PPO.update (ppo.py:94-178): mean value / surrogate / adaptation losses.  With ``async_losses`` set (the Runner
@@ -384,14 +405,14 @@ class PPO:
         mean_adaptation_module_loss = torch.zeros((), device=self.device)
         ac = self.actor_critic
         params = list(ac.parameters())
-        gen = self.storage.mini_batch_generator(PPO_Args.num_mini_batches, PPO_Args.num_learning_epochs)
+        gen = self.storage.mini_batch_generator(self.args.num_mini_batches, self.args.num_learning_epochs)
         for (obs_b, critic_obs_b, priv_b, hist_b, actions_b, target_values_b, adv_b, returns_b, old_logp_b, old_mu_b,
              old_sigma_b, masks_b, env_bins_b) in gen:
             ac.act(obs_b, priv_b, masks=masks_b)
             logp_b = ac.get_actions_log_prob(actions_b)
             value_b = ac.evaluate(critic_obs_b, priv_b, masks=masks_b)
             mu_b, sigma_b, entropy_b = ac.action_mean, ac.action_std, ac.entropy
-            if PPO_Args.desired_kl is not None and PPO_Args.schedule == "adaptive":
+            if self.args.desired_kl is not None and self.args.schedule == "adaptive":
                 with torch.inference_mode():
                     kl = torch.sum(torch.log(sigma_b / old_sigma_b + 1.e-5) + (
                         torch.square(old_sigma_b) + torch.square(old_mu_b - mu_b)) / (2.0 * torch.square(sigma_b))
@@ -401,46 +422,36 @@ class PPO:
                         kl_mean = _all_reduce_(kl_mean.clone())
                         kl_mean /= _world()
                     kl_mean = kl_mean.item()
-                    if kl_mean > PPO_Args.desired_kl * 2.0:
+                    if kl_mean > self.args.desired_kl * 2.0:
                         self.learning_rate = max(1e-5, self.learning_rate / 1.5)
-                    elif kl_mean < PPO_Args.desired_kl / 2.0 and kl_mean > 0.0:
+                    elif kl_mean < self.args.desired_kl / 2.0 and kl_mean > 0.0:
                         self.learning_rate = min(1e-2, self.learning_rate * 1.5)
                     for g in self.optimizer.param_groups:
                         g["lr"] = self.learning_rate
             ratio = torch.exp(logp_b - torch.squeeze(old_logp_b))
             surrogate = -torch.squeeze(adv_b) * ratio
-            surrogate_clipped = -torch.squeeze(adv_b) * torch.clamp(ratio, 1.0 - PPO_Args.clip_param,
-                                                                   1.0 + PPO_Args.clip_param)
+            surrogate_clipped = -torch.squeeze(adv_b) * torch.clamp(ratio, 1.0 - self.args.clip_param,
+                                                                   1.0 + self.args.clip_param)
             surrogate_loss = torch.max(surrogate, surrogate_clipped).mean()
-            if PPO_Args.use_clipped_value_loss:
-                value_clipped = target_values_b + (value_b - target_values_b).clamp(-PPO_Args.clip_param,
-                                                                                    PPO_Args.clip_param)
+            if self.args.use_clipped_value_loss:
+                value_clipped = target_values_b + (value_b - target_values_b).clamp(-self.args.clip_param,
+                                                                                    self.args.clip_param)
                 value_loss = torch.max((value_b - returns_b).pow(2), (value_clipped - returns_b).pow(2)).mean()
             else:
                 value_loss = (returns_b - value_b).pow(2).mean()
-            loss = surrogate_loss + PPO_Args.value_loss_coef * value_loss - PPO_Args.entropy_coef * entropy_b.mean()
+            loss = surrogate_loss + self.args.value_loss_coef * value_loss - self.args.entropy_coef * entropy_b.mean()
             self.optimizer.zero_grad()
             loss.backward()
             if self.grad_allreduce:
                 self._allreduce_grads(params)
-            nn.utils.clip_grad_norm_(params, PPO_Args.max_grad_norm)
+            nn.utils.clip_grad_norm_(params, self.args.max_grad_norm)
             self.optimizer.step()
             mean_value_loss += value_loss.detach()
             mean_surrogate_loss += surrogate_loss.detach()
-            for _ in range(PPO_Args.num_adaptation_module_substeps):
-                adaptation_pred = ac.adaptation_module(hist_b)
-                with torch.no_grad():
-                    adaptation_target = ac.env_factor_encoder(priv_b)
-                adaptation_loss = F.mse_loss(adaptation_pred, adaptation_target)
-                self.adaptation_module_optimizer.zero_grad()
-                adaptation_loss.backward()
-                if self.grad_allreduce:
-                    self._allreduce_grads(params)
-                self.adaptation_module_optimizer.step()
-                mean_adaptation_module_loss += adaptation_loss.detach()
-        num_updates = PPO_Args.num_learning_epochs * PPO_Args.num_mini_batches
+            mean_adaptation_module_loss += self._adaptation_substeps(hist_b, priv_b, params)
+        num_updates = self.args.num_learning_epochs * self.args.num_mini_batches
         out = torch.stack([mean_value_loss / num_updates, mean_surrogate_loss / num_updates,
-                           mean_adaptation_module_loss / (num_updates * PPO_Args.num_adaptation_module_substeps)])
+                           mean_adaptation_module_loss / (num_updates * self.args.num_adaptation_module_substeps)])
         self.storage.clear()
         mv, ms, ma = out.tolist()
         return mv, ms, ma

@@ -49,15 +49,21 @@ class Logger(ML_Logger):
 
 
 class Runner:
-    def __init__(self, env, device="cpu", seed=0, logger=None):
+    # the classes a runner is built from (lrl.hlp's Runner names its own)
+    args = RunnerArgs
+    actor_critic_class = ActorCritic
+    alg_class = PPO
+
+    def __init__(self, env, device="cpu", seed=0, logger=None, fused=None):
+        """``fused``: the algorithm's native path (None: on for a GPU device; False: the torch-autograd form)."""
         self.device = device
         self.env = env
-        ac = ActorCritic(self.env.num_obs, self.env.num_privileged_obs, self.env.num_obs_history,
-                         self.env.num_actions).to(self.device)
-        self.alg = PPO(ac, device=self.device, seed=seed)
+        ac = self.actor_critic_class(self.env.num_obs, self.env.num_privileged_obs, self.env.num_obs_history,
+                                     self.env.num_actions).to(self.device)
+        self.alg = self.alg_class(ac, device=self.device, fused=fused, seed=seed)
         self.alg.row_offset = int(getattr(env, "env_offset", 0))  # policy noise keyed by global env id (sharded ranks)
         self.alg.async_losses = not _SYNC_UPDATE  # losses logged as device scalars: no host sync per iteration
-        self.num_steps_per_env = RunnerArgs.num_steps_per_env
+        self.num_steps_per_env = self.args.num_steps_per_env
         self.alg.init_storage(self.env.num_train_envs, self.num_steps_per_env, [self.env.num_obs],
                               [self.env.num_privileged_obs], [self.env.num_obs_history], [self.env.num_actions])
         self.tot_timesteps = 0
@@ -98,10 +104,10 @@ class Runner:
             lg.store_metrics(time_elapsed=lg.since("start"), time_iter=lg.split("epoch"), adaptation_loss=ma,
                              mean_value_loss=mv, mean_surrogate_loss=ms)
             self.tot_timesteps += self.num_steps_per_env * self.env.num_envs
-            if lg.every(RunnerArgs.log_freq, "iteration", start_on=1):
+            if lg.every(self.args.log_freq, "iteration", start_on=1):
                 lg.log_metrics_summary(key_values={"timesteps": self.tot_timesteps, "iterations": it})
                 lg.job_running()
-            if RunnerArgs.save_interval and it % RunnerArgs.save_interval == 0:
+            if self.args.save_interval and it % self.args.save_interval == 0:
                 self.save(it)
         self.current_learning_iteration += num_learning_iterations
         if num_learning_iterations > 0:  # the reference always saves after the loop (__init__.py:246-265)
