@@ -75,6 +75,70 @@ def golden(name):
     return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
 
 
+def init_params(module):
+    """Same deterministic init as tests/golden/make_golden.py::init_params (std = 1)."""
+    import zlib
+
+    import torch
+    with torch.no_grad():
+        for name, p in module.named_parameters():
+            r = np.random.default_rng(zlib.crc32(name.encode()))
+            fan_in = p.shape[-1] if p.dim() > 1 else 1
+            scale = 1.0 / np.sqrt(fan_in) if p.dim() > 1 else 0.05
+            if name == "std":
+                p.copy_(torch.ones_like(p))
+            else:
+                p.copy_(torch.tensor(r.uniform(-1, 1, tuple(p.shape)) * scale, dtype=torch.float))
+
+
+def autograd_minibatch(ac, args, b, dtype, priv=None, hist=None):
+    """The reference's loss (ppo.py:104-146) on one minibatch under torch autograd in ``dtype``, for either net.
+
+    ``args`` carries clip_param, value_loss_coef, entropy_coef and use_clipped_value_loss (a PPO_Args class or any
+    object with these names); ``b`` = (obs, actions, target values, returns, old log-probs, advantages, old mu, old
+    sigma), the minibatch's rows.  ``priv``: the privileged rows of the teacher net (None for the plain net);
+    ``hist``: the history rows — the adaptation module's regression (ppo.py:157-166) is then run as well, its
+    gradients land in the same dict.  Returns a namespace: kl, value_loss, surrogate, adaptation_loss (floats),
+    grads {name: grad}, and the per-row ratio and value (detached) for checks of the inputs."""
+    import copy
+    import types
+
+    import torch
+    import torch.nn.functional as F
+    m = copy.deepcopy(ac).to(dtype)
+    obs, act, tv, ret, oldlp, adv, omu, osig = (x.to(dtype) for x in b)
+    priv = None if priv is None else priv.to(dtype)
+    m.zero_grad(set_to_none=True)
+    m.act(obs, priv)
+    logp = m.get_actions_log_prob(act)
+    value = m.evaluate(obs, priv)
+    mu, sigma, ent = m.action_mean, m.action_std, m.entropy
+    with torch.no_grad():
+        kl = torch.sum(torch.log(sigma / osig + 1.e-5) + (torch.square(osig) + torch.square(omu - mu)) /
+                       (2.0 * torch.square(sigma)) - 0.5, axis=-1).mean().item()
+    ratio = torch.exp(logp - torch.squeeze(oldlp))
+    surr = torch.max(-torch.squeeze(adv) * ratio,
+                     -torch.squeeze(adv) * torch.clamp(ratio, 1 - args.clip_param, 1 + args.clip_param)).mean()
+    if args.use_clipped_value_loss:
+        vc = tv + (value - tv).clamp(-args.clip_param, args.clip_param)
+        vl = torch.max((value - ret).pow(2), (vc - ret).pow(2)).mean()
+    else:
+        vl = (ret - value).pow(2).mean()
+    loss = surr + args.value_loss_coef * vl - args.entropy_coef * ent.mean()
+    loss.backward()
+    al = None
+    if hist is not None:
+        pred = m.adaptation_module(hist.to(dtype))
+        with torch.no_grad():
+            target = m.env_factor_encoder(priv)
+        al = F.mse_loss(pred, target)
+        al.backward()
+        al = al.item()
+    return types.SimpleNamespace(kl=kl, value_loss=vl.item(), surrogate=surr.item(), adaptation_loss=al,
+                                 grads={k: p.grad for k, p in m.named_parameters()}, ratio=ratio.detach(),
+                                 value=value.detach())
+
+
 # fp32 kernel vs the fp64 oracle after the 4 sub-steps of a step, per field (atol, rtol): |got - ref| <= atol + rtol |ref|
 # for every element.  Set from the measured error distribution (round 4, profiles/r4b_parity_stats.jsonl, 128 compared
 # steps / 89,344 env-steps of every physics test: scripts/parity_stats_summary.py): each bar sits 2-25x above the

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import GOLDEN, golden
+from helpers import GOLDEN, autograd_minibatch, golden
 from lrl import _abi
 
 pytestmark = pytest.mark.gpu
@@ -201,26 +201,10 @@ def _random_storage(alg, seed=1):
 
 
 def _autograd_minibatch(ac, args, b, dtype):
-    """The reference's loss (ppo.py:104-146) on one minibatch in `dtype`: (kl, value loss, surrogate, {name: grad})."""
-    import copy
-    m = copy.deepcopy(ac).to(dtype)
-    obs, act, tv, ret, oldlp, adv, omu, osig = (x.to(dtype) for x in b)
-    m.zero_grad(set_to_none=True)
-    m.act(obs, None)
-    logp = m.get_actions_log_prob(act)
-    value = m.evaluate(obs, None)
-    mu, sigma, ent = m.action_mean, m.action_std, m.entropy
-    with torch.no_grad():
-        kl = torch.sum(torch.log(sigma / osig + 1.e-5) + (torch.square(osig) + torch.square(omu - mu)) /
-                       (2.0 * torch.square(sigma)) - 0.5, axis=-1).mean().item()
-    ratio = torch.exp(logp - torch.squeeze(oldlp))
-    surr = torch.max(-torch.squeeze(adv) * ratio,
-                     -torch.squeeze(adv) * torch.clamp(ratio, 1 - args.clip_param, 1 + args.clip_param)).mean()
-    vc = tv + (value - tv).clamp(-args.clip_param, args.clip_param)
-    vl = torch.max((value - ret).pow(2), (vc - ret).pow(2)).mean()
-    loss = surr + args.value_loss_coef * vl - args.entropy_coef * ent.mean()
-    loss.backward()
-    return kl, vl.item(), surr.item(), {k: p.grad for k, p in m.named_parameters()}
+    """The reference's loss (ppo.py:104-146) on one minibatch in `dtype`: (kl, value loss, surrogate, {name: grad});
+    the restatement itself is helpers.autograd_minibatch."""
+    r = autograd_minibatch(ac, args, b, dtype)
+    return r.kl, r.value_loss, r.surrogate, r.grads
 
 
 @pytest.mark.parametrize("N,T", [(37, 20), (972, 200)])
