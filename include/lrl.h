@@ -576,8 +576,11 @@ int32_t lrl_ppo_timing(int32_t enable, double* total_ms, int64_t* launches);
 /* Development switch of the update's GEMM kernels (tests compare them in one process): bit 0 set = no pre-split-B
  * kernel for the weight products, bit 1 set = no LDS-DMA weight-gradient kernel, bit 2 set = no LDS-DMA
  * forward / backward-data kernel (the fp32-staged x6 kernel takes those products instead); bit 3 set (bit 2 clear) =
- * the LDS-DMA kernel for every forward / backward-data product it fits (it is off by default).  Returns the previous
- * mask. */
+ * the LDS-DMA kernel for every forward / backward-data product it fits (it is off by default); bit 4 set = none of the
+ * bf16-split families (the fp32-staged x6 kernel, both LDS-DMA forms of it, and the pre-split-B kernel unless the caller
+ * itself hands planes over: lrl_gemm_f32 layout | 0x100, lrl_gemm_desc.planes), so every product falls through to the
+ * fp32 MFMA families, as with LRL_GEMM_X6=0 in the environment; bit 5 set = the 32-row thin kernel instead of the
+ * 16-row one (as LRL_THIN16=0).  Returns the previous mask. */
 int32_t lrl_debug_gemm_paths(int32_t disable_mask);
 
 /* Determinism probe: with mode != 0 every lrl_sim_step of `s` launches, right before its env kernel, a pass that
@@ -600,6 +603,52 @@ int32_t lrl_debug_sim_arena(lrl_sim* s, void** arena, int64_t* bytes, int64_t* s
 int32_t lrl_gemm_f32(int32_t layout, int32_t epi, int32_t M, int32_t N, int32_t K, const float* A, int64_t lda,
                      const float* B, int64_t ldb, float* C, int64_t ldc, const float* bias, const float* aux,
                      int64_t ld_aux, const int64_t* rows, float* workspace, int64_t workspace_floats, void* stream);
+
+/* Kernel family of a product, the low byte of the path report of lrl_gemm_f32_ex; the report is
+ * family | bm << 8 | bn << 16 | interior << 24 (bm x bn: the workgroup's output tile; interior: the unguarded
+ * instantiation of the fp32-staged bf16-split kernel). */
+enum {
+  LRL_GEMM_PATH_X6P = 1,      /* bf16 split, pre-split B planes, LDS-DMA */
+  LRL_GEMM_PATH_X6T = 2,      /* bf16 split, LDS-DMA weight gradient */
+  LRL_GEMM_PATH_X6 = 3,       /* bf16 split while staging through registers */
+  LRL_GEMM_PATH_X6D = 4,      /* bf16 split, LDS-DMA forward / backward-data */
+  LRL_GEMM_PATH_GLDS = 5,     /* fp32 MFMA, LDS-DMA, 16-k stages */
+  LRL_GEMM_PATH_GLDS32 = 6,   /* fp32 MFMA, LDS-DMA, 32-k stages */
+  LRL_GEMM_PATH_GLDS_TN = 7,  /* fp32 MFMA, LDS-DMA weight gradient */
+  LRL_GEMM_PATH_THIN16 = 8,   /* fp32 MFMA, B in registers, 16-row tiles */
+  LRL_GEMM_PATH_THIN32 = 9,   /* the same, 32-row tiles */
+  LRL_GEMM_PATH_STAGED = 10,  /* fp32 MFMA, register-staged */
+};
+
+/* lrl_gemm_f32 with the operand forms the update itself uses: `groups` independent products of one shape whose
+ * operands sit ga / gb / gc / gbias / gaux elements apart (column offsets inside a shared row pitch, or whole
+ * matrices), any pitch, any base.
+ *   NT / NN: C (ldc, gc) receives the product; bias [n] per group (gbias apart), aux [m][n] (ld_aux, gaux); rows
+ *     gathers A's rows.  planes != 0: op(B) of every group is first split into bf16 planes in the workspace
+ *     (3 * groups * N * round16(K) / 2 floats) and the product must run on the pre-split-B kernel, or the call fails.
+ *   TN: split-k exactly as the update lays it out: partials [split][group][M][N] in the workspace, the bias-gradient
+ *     partials [split][group][M] behind them (splits * groups * (M * N + M) floats), then one segmented reduction into
+ *     C [groups][M][N] (contiguous: ldc == N; gc is not used) and, when bias is not NULL, db = bias [groups][M] (the
+ *     field is written).  rows gathers B's rows.  splits 0 = the update's own split count; any other count is an
+ *     override, refused if it leaves a split without rows.
+ * path_out / splits_out (each may be NULL) receive the path report (above) and the split count that ran. */
+typedef struct lrl_gemm_desc {
+  int32_t layout, epi, M, N, K;
+  int32_t groups, planes, splits;
+  const float* A;
+  const float* B;
+  float* C;
+  float* bias;
+  const float* aux;
+  const int64_t* rows;
+  float* workspace;
+  int64_t lda, ldb, ldc, ld_aux;
+  int64_t ga, gb, gc, gbias, gaux;
+  int64_t workspace_floats;
+  int32_t* path_out;
+  int32_t* splits_out;
+} lrl_gemm_desc;
+int32_t lrl_gemm_f32_ex(const lrl_gemm_desc* d, void* stream);
 
 /* reset_idx's episode logging (legged_robot.py:261-276) for `rows` rows of a [rows][ld] f32 device table at once:
  * means[r] = mean over the n env ids of table[r][ids] (fixed-order reduction), then, when `zero`, those entries are

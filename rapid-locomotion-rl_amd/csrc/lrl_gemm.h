@@ -9,7 +9,8 @@
 // the weight gradient) may be gathered through an int64 row list — the minibatch indices of
 // RolloutStorage.mini_batch_generator (rollout_storage.py:100-137) — so the minibatch is never copied.
 //
-// Three kernels behind one launcher (gemm_launch picks by shape):
+// The fp32 MFMA kernels behind the launcher (gemm_launch picks by shape; the bf16-split families it tries first —
+// x6, x6d, x6p, x6t — are described in lrl_gemm.hip, the dispatch table is DESIGN.md §3):
 //  * LDS-DMA (NT / NN, every tile interior, float4-aligned operands): 64 x 64 tile, 16-k slices land in a
 //    3-stage LDS ring straight from global memory (global_load_lds_dwordx4, counted vmcnt waits, swizzled
 //    images read with ds_read_b128), two accumulators per wave;
@@ -96,7 +97,16 @@ enum GemmLayout : int { GEMM_NT = 0, GEMM_NN = 2, GEMM_TN = 3 };
 // lrl error code (bad shape / unsupported layout).
 int gemm_launch(const GemmP& p, int layout, int epi, int groups, void* stream);
 
-// 1 when this thread's last gemm_launch ran the x6p kernel (test entry point)
+// Kernel family of a launch (the LRL_GEMM_PATH_* values of include/lrl.h)
+enum GemmFamily : int {
+  FAM_NONE = 0, FAM_X6P = 1, FAM_X6T = 2, FAM_X6 = 3, FAM_X6D = 4, FAM_GLDS = 5, FAM_GLDS32 = 6, FAM_GLDS_TN = 7,
+  FAM_THIN16 = 8, FAM_THIN32 = 9, FAM_STAGED = 10,
+};
+// family | bm << 8 | bn << 16 | interior << 24 (interior: gemm_x6_kernel's unguarded instantiation)
+constexpr int gemm_path_id(int family, int bm, int bn, bool interior) {
+  return family | (bm << 8) | (bn << 16) | (interior ? 1 << 24 : 0);
+}
+// The family and tile this thread's last gemm_launch ran on, as a gemm_path_id (0: nothing launched)
 int gemm_last_path();
 
 // How a weight-gradient product (reduction over K rows, `groups` problems) is split: the split count.

@@ -22,6 +22,19 @@ constexpr int GBK = LRL_GBK;  // k-slice per LDS stage
 constexpr int KQ = GBK / 4;   // float4 items per k-contiguous row slice
 constexpr int GTHREADS = 256;
 
+// run-time path mask (lrl_debug_gemm_paths: tests compare the paths in one process): bit 0 = no x6p, bit 1 = no x6t,
+// bit 2 = no x6d, bit 3 = x6d on (NT and NN) unless bit 2, bit 4 = no bf16-split family at all (x6, x6d, x6t, and x6p
+// unless the caller hands planes over: the fp32 MFMA families take every product), bit 5 = the 32-row thin kernel
+// instead of the 16-row one
+static int g_path_off = 0;
+static int path_off() { return __atomic_load_n(&g_path_off, __ATOMIC_RELAXED); }
+
+// family / tile of this thread's last launch (gemm_last_path): one thread-local store per launch
+static thread_local int g_last_path = 0;
+static inline void note_path(int family, int bm, int bn, bool interior = false) {
+  g_last_path = gemm_path_id(family, bm, bn, interior);
+}
+
 template <int BM, int BN, int LAYOUT>
 struct GemmTile {
   static constexpr bool AMC = (LAYOUT & 1) != 0;
@@ -787,13 +800,13 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_thin16_kernel(GemmP p) {
   }
 }
 
-// (LRL_THIN16=0: development switch back to the 32-row tiles)
+// (LRL_THIN16=0, or bit 5 of lrl_debug_gemm_paths: development switch back to the 32-row tiles)
 static bool thin16_enabled() {
   static const int on = [] {
     const char* e = getenv("LRL_THIN16");
     return e && e[0] == '0' ? 0 : 1;
   }();
-  return on != 0;
+  return on != 0 && !(path_off() & 32);
 }
 
 template <int LAYOUT, int EPI, int NBK>
@@ -809,11 +822,13 @@ static int launch_thin_k(const GemmP& p, int groups, hipStream_t st) {
     const int mt = (p.M + 15) / 16;
     const int gx = std::max(1, std::min(mt, 2 * ncu / std::max(1, groups)));
     hipLaunchKernelGGL((gemm_thin16_kernel<LAYOUT, EPI, NBK>), dim3(gx, groups), dim3(GTHREADS), 0, st, p);
+    note_path(FAM_THIN16, 16, 32);
     return 0;
   }
   const int mt = (p.M + 31) / 32;
   const int gx = std::max(1, std::min(mt, 2 * ncu / std::max(1, groups)));
   hipLaunchKernelGGL((gemm_thin_kernel<LAYOUT, EPI, NBK>), dim3(gx, groups), dim3(GTHREADS), 0, st, p);
+  note_path(FAM_THIN32, 32, 32);
   return 0;
 }
 template <int LAYOUT, int EPI>
@@ -969,6 +984,7 @@ static int launch_glds_tn_tag(const GemmP& p, int groups, hipStream_t st) {
   }
   dim3 gt((p.M / 128) * ((p.N + BN - 1) / BN) * groups * p.splits);
   hipLaunchKernelGGL((gemm_glds_tn_kernel<3, BN, SHAPE>), gt, dim3(GTHREADS), lds, st, p);
+  note_path(FAM_GLDS_TN, 128, BN);
   return hipGetLastError() == hipSuccess ? 0 : LRL_E_HIP;
 }
 
@@ -1396,16 +1412,18 @@ static int launch_x6_tile(const GemmP& p, int layout, int epi, int groups, hipSt
   }
 #undef LRL_X6
 #undef LRL_X6G
+  note_path(FAM_X6, BM, BN, interior);
   return hipGetLastError() == hipSuccess ? 0 : LRL_E_HIP;
 }
 
-// x6 path switch: LRL_GEMM_X6=0 keeps every product on the fp32 MFMA kernels (A/B comparisons)
+// bf16-split switch: LRL_GEMM_X6=0 (or bit 4 of lrl_debug_gemm_paths) keeps every product on the fp32 MFMA kernels
+// (A/B comparisons): no x6, x6d or x6t, and no x6p unless the caller itself hands planes over
 static bool x6_enabled() {
   static const int on = [] {
     const char* e = getenv("LRL_GEMM_X6");
     return e && e[0] == '0' ? 0 : 1;
   }();
-  return on != 0;
+  return on != 0 && !(path_off() & 16);
 }
 
 static int try_x6d(const GemmP& p, int layout, int epi, int groups, int bm, int bn, hipStream_t st);
@@ -1793,10 +1811,6 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6t_kernel(GemmP p) {
   }
 }
 
-// run-time path mask (lrl_debug_gemm_paths: tests compare the paths in one process): bit 0 off = no x6p, bit 1 = no x6t,
-// bit 2 = no x6d, bit 3 = x6d on (NT and NN) unless bit 2
-static int g_path_off = 0;
-
 // ---------------------------------------------------------------------------------------------------
 // x6 forward / backward-data with LDS-DMA staging ("x6d", NT / NN, fp32 operands): gemm_x6t_kernel's structure for
 // the batch-major products.  Both operands land fp32 by LDS-DMA in a 3-deep ring of 16-k stages (counted vmcnt, raw
@@ -2006,7 +2020,7 @@ static int x6d_mode() {
     const char* e = getenv("LRL_GEMM_X6D");
     return e ? atoi(e) : 0;
   }();
-  const int off = __atomic_load_n(&g_path_off, __ATOMIC_RELAXED);
+  const int off = path_off();
   return (off & 4) ? 0 : (off & 8) ? 2 : m;
 }
 static bool x6d_enabled() { return x6d_mode() != 0; }
@@ -2030,6 +2044,7 @@ static int try_x6d(const GemmP& p, int layout, int epi, int groups, int bm, int 
     case 6: launch_x6d_l<128, 64, GEMM_NN>(p, epi, groups, st); break;
     default: launch_x6d_l<128, 128, GEMM_NN>(p, epi, groups, st); break;
   }
+  note_path(FAM_X6D, bm, bn);
   return hipGetLastError() == hipSuccess ? 1 : LRL_E_HIP;
 }
 // x6t path switch: LRL_GEMM_X6T=0 keeps the weight gradients on gemm_x6_kernel
@@ -2038,7 +2053,7 @@ static bool x6t_enabled() {
     const char* e = getenv("LRL_GEMM_X6T");
     return e && e[0] == '0' ? 0 : 1;
   }();
-  return on != 0 && !(__atomic_load_n(&g_path_off, __ATOMIC_RELAXED) & 2);
+  return on != 0 && x6_enabled() && !(path_off() & 2);
 }
 
 // returns 1 when launched on the x6t kernel (0: not eligible, <0: error).  n may be ragged when B's row pitch covers
@@ -2051,6 +2066,7 @@ static int try_x6t(const GemmP& p, int layout, int epi, int groups, hipStream_t 
   if (p.b_rows && p.kps > X6T_MAX_GATHER_KPS) return 0;
   if ((int64_t)(p.splits - 1) * p.kps >= p.K) return 0;  // (every split has a non-empty range)
   dim3 grid((unsigned)((p.M / 128) * nt * groups * p.splits));  // (stores stop at p.N)
+  note_path(FAM_X6T, 128, bn);
   if (bn == 64) {
     if (p.b_rows) hipLaunchKernelGGL((gemm_x6t_kernel<64, 5, true>), grid, dim3(GTHREADS), 0, st, p);
     else hipLaunchKernelGGL((gemm_x6t_kernel<64, 3, false>), grid, dim3(GTHREADS), 0, st, p);
@@ -2077,14 +2093,14 @@ static bool x6p_enabled() {
     const char* e = getenv("LRL_GEMM_X6P");
     return e && e[0] == '1' ? 1 : 0;
   }();
-  return on != 0 && !(__atomic_load_n(&g_path_off, __ATOMIC_RELAXED) & 1);
+  return on != 0 && x6_enabled() && !(path_off() & 1);
 }
 
 bool gemm_x6p_enabled() { return x6p_enabled(); }
 
 // returns 1 when launched on the x6p kernel (0: not eligible, <0: error)
 static int try_x6p(const GemmP& p, int layout, int epi, int groups, hipStream_t st) {
-  if (!p.bpl || (__atomic_load_n(&g_path_off, __ATOMIC_RELAXED) & 1) || (layout != GEMM_NT && layout != GEMM_NN) ||
+  if (!p.bpl || (path_off() & 1) || (layout != GEMM_NT && layout != GEMM_NN) ||
       p.splits != 1)
     return 0;
   if (epi != EPI_STORE && !epi_bias(epi) && !epi_aux(epi)) return 0;
@@ -2115,6 +2131,7 @@ static int try_x6p(const GemmP& p, int layout, int epi, int groups, hipStream_t 
   }
 #undef LRL_X6P_E
 #undef LRL_X6P
+  note_path(FAM_X6P, big ? 128 : 64, 128);
   return hipGetLastError() == hipSuccess ? 1 : LRL_E_HIP;
 }
 
@@ -2243,7 +2260,6 @@ int gemm_pick_splits(int M, int N, int K, int groups) {
   return splits;
 }
 
-static thread_local int g_last_path = 0;
 int gemm_last_path() { return g_last_path; }
 
 int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) {
@@ -2269,14 +2285,8 @@ int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) 
             layout, epi, p.M, p.N, p.K, groups, p.splits, p.avec, p.bvec, p.a_rows != nullptr, p.b_rows != nullptr);
   // weight products with a pre-split B: the LDS-DMA x6p kernel
   g_last_path = 0;
-  if (int xr = try_x6p(p, layout, epi, groups, st)) {
-    if (xr > 0) g_last_path = 1;
-    return xr > 0 ? 0 : xr;
-  }
-  if (int xr = try_x6t(p, layout, epi, groups, st)) {
-    if (xr > 0) g_last_path = 2;
-    return xr > 0 ? 0 : xr;
-  }
+  if (int xr = try_x6p(p, layout, epi, groups, st)) return xr > 0 ? 0 : xr;
+  if (int xr = try_x6t(p, layout, epi, groups, st)) return xr > 0 ? 0 : xr;
   // fp32 on the bf16 MFMA (exact split, fp32-class error) wherever the tile shapes fit
   if (int xr = try_x6(p, layout, epi, groups, st)) return xr > 0 ? 0 : xr;
   // LDS-DMA path: batch-major product, every tile interior, float4-aligned operands, single split
@@ -2303,6 +2313,7 @@ int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) 
       else LRL_GLDS(GEMM_NN, EPI_DELU);
     }
 #undef LRL_GLDS
+    note_path(bk32 ? FAM_GLDS32 : FAM_GLDS, 64, 64);
     return hipGetLastError() == hipSuccess ? 0 : LRL_E_HIP;
   }
   // LDS-DMA weight gradient: 128-row m tiles, 128-wide n tiles whose reads stay inside the row pitch,
@@ -2342,6 +2353,7 @@ int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) 
   else if (bm == 128 && bn == 32) rc = launch_bm<128, 32>(p, layout, epi, grid, st);
   else if (bm == 32 && bn == 128) rc = launch_bm<32, 128>(p, layout, epi, grid, st);
   if (rc) return rc;
+  note_path(FAM_STAGED, bm, bn);
   return hipGetLastError() == hipSuccess ? 0 : LRL_E_HIP;
 }
 

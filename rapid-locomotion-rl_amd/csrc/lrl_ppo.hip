@@ -1984,10 +1984,74 @@ extern "C" int32_t lrl_gemm_f32(int32_t layout, int32_t epi, int32_t M, int32_t 
     gemm_use_planes(p, j);
     int rc = gemm_launch(p, layout, epi, 1, st);
     if (rc) return lrl_set_error(rc, "lrl_gemm_f32: launch failure");
-    return gemm_last_path() == 1 ? 0 : lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32: shape not eligible for the x6p kernel");
+    return (gemm_last_path() & 0xff) == FAM_X6P
+               ? 0
+               : lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32: shape not eligible for the x6p kernel");
   }
   int rc = gemm_launch(p, layout, epi, 1, st);
   return rc ? lrl_set_error(rc, "lrl_gemm_f32: bad layout/epilogue or launch failure") : 0;
+}
+
+// ---- GEMM test entry point, the update's grouped / pitched operand forms ----
+extern "C" int32_t lrl_gemm_f32_ex(const lrl_gemm_desc* d, void* stream) {
+  if (!d || !d->A || !d->B || !d->C || d->M <= 0 || d->N <= 0 || d->K <= 0 || d->groups <= 0 || d->splits < 0)
+    return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: bad argument");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int layout = d->layout, epi = d->epi, groups = d->groups, M = d->M, N = d->N, K = d->K;
+  if (d->path_out) *d->path_out = 0;
+  GemmP p{};
+  p.A = d->A; p.lda = d->lda; p.B = d->B; p.ldb = d->ldb; p.aux = d->aux; p.ld_aux = d->ld_aux;
+  p.M = M; p.N = N; p.K = K; p.splits = 1;
+  p.ga = d->ga; p.gb = d->gb; p.gaux = d->gaux;
+  int splits = 1;
+  if (layout == GEMM_TN) {
+    // G::tn's layout: [split][group][M][N] partials, [split][group][M] bias partials behind them, one reduction
+    if (epi != EPI_PARTIAL || d->planes) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: TN is epi 4, no planes");
+    if (d->ldc != N) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: TN needs ldc == N");
+    splits = d->splits ? d->splits : gemm_pick_splits(M, N, K, groups);
+    const int kps = ((K + splits - 1) / splits + 15) / 16 * 16;  // (gemm_launch rounds a split to whole 16-row slices)
+    // (only an override is judged: the update's own count stands as it is)
+    if (d->splits && (int64_t)(splits - 1) * kps >= K)
+      return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: a split would be empty");
+    const int64_t gmn = (int64_t)groups * M * N, gm = (int64_t)groups * M;
+    if (!d->workspace || (int64_t)splits * (gmn + gm) > d->workspace_floats)
+      return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: workspace too small");
+    p.b_rows = d->rows; p.splits = splits; p.kps = (K + splits - 1) / splits;
+    p.gc = (int64_t)M * N; p.ldc = N; p.part_stride = gmn;
+    p.C = d->workspace;
+    p.bias_part = d->workspace + (int64_t)splits * gmn;
+    if (int rc = gemm_launch(p, GEMM_TN, EPI_PARTIAL, groups, st)) return lrl_set_error(rc, "lrl_gemm_f32_ex: launch failed");
+    SegList L{};
+    L.s[L.n++] = Seg{d->workspace, d->C, gmn, gmn, splits, 1.f};
+    if (d->bias) L.s[L.n++] = Seg{p.bias_part, d->bias, gm, gm, splits, 1.f};
+    launch_seg(L, st);
+  } else {
+    if (layout != GEMM_NT && layout != GEMM_NN) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: layout is 0, 2 or 3");
+    if (d->splits > 1 || epi == EPI_PARTIAL) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: NT / NN are not split");
+    if ((epi == EPI_BIAS_TANH && layout != GEMM_NT) || (epi == EPI_DTANH && layout != GEMM_NN))
+      return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: epi 5 is an NT epilogue, epi 6 an NN one");
+    if ((epi == EPI_DELU || epi == EPI_DTANH) && !d->aux) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: epi 3 / 6 need aux");
+    if ((epi == EPI_BIAS || epi == EPI_BIAS_ELU || epi == EPI_BIAS_TANH) && !d->bias)
+      return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: epi 1 / 2 / 5 need bias");
+    p.C = d->C; p.ldc = d->ldc; p.gc = d->gc; p.bias = d->bias; p.gbias = d->gbias; p.a_rows = d->rows;
+    PlaneJob j{};
+    if (d->planes) {
+      j.W = d->B; j.ldw = d->ldb; j.gsrc = d->gb; j.groups = groups; j.trans = layout == GEMM_NN ? 1 : 0;
+      j.rows = layout == GEMM_NN ? K : N; j.cols = layout == GEMM_NN ? N : K;
+      j.dst = reinterpret_cast<uint16_t*>(d->workspace);
+      if (!d->workspace || plane_elems(j) > 2 * d->workspace_floats)
+        return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: workspace too small for the planes");
+      if (int rc = x6_planes_launch(&j, 1, st)) return lrl_set_error(rc, "lrl_gemm_f32_ex: planes launch failed");
+      gemm_use_planes(p, j);
+    }
+    if (int rc = gemm_launch(p, layout, epi, groups, st))
+      return lrl_set_error(rc, "lrl_gemm_f32_ex: bad layout/epilogue or launch failure");
+    if (d->planes && (gemm_last_path() & 0xff) != FAM_X6P)
+      return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: shape not eligible for the x6p kernel");
+  }
+  if (d->path_out) *d->path_out = gemm_last_path();
+  if (d->splits_out) *d->splits_out = splits;
+  return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_gemm_f32_ex: launch failed");
 }
 
 // ---- timing hook of the dominant update product (bench.py roofline) ----

@@ -58,6 +58,8 @@ printf("%zu %zu %zu %zu %zu %zu\n", sizeof(lrl_ppo_net), offsetof(lrl_ppo_net, t
  offsetof(lrl_ppo_batch, batch), sizeof(lrl_ppo_hparams), sizeof(lrl_ppo_ctrl));
 printf("%zu %zu\n", offsetof(lrl_ppo_batch, hist_ld), offsetof(lrl_rollout_store, hist_ld));
 printf("%zu %zu %zu\n", sizeof(lrl_dev_curriculum), offsetof(lrl_dev_curriculum, nz), offsetof(lrl_dev_curriculum, draws));
+printf("%zu %zu %zu %zu %zu %zu\n", sizeof(lrl_gemm_desc), offsetof(lrl_gemm_desc, splits), offsetof(lrl_gemm_desc, A),
+ offsetof(lrl_gemm_desc, lda), offsetof(lrl_gemm_desc, workspace_floats), offsetof(lrl_gemm_desc, splits_out));
 return 0;}
 """
     exe = str(tmp_path / "lrl_layout_check")
@@ -71,7 +73,9 @@ return 0;}
                    C.sizeof(_abi.LrlRolloutStore), C.sizeof(_abi.LrlPpoNet), _abi.LrlPpoNet.total.offset,
                    C.sizeof(_abi.LrlPpoBatch), _abi.LrlPpoBatch.batch.offset, C.sizeof(_abi.LrlPpoHparams),
                    _abi.PPO_CTRL_BYTES, _abi.LrlPpoBatch.hist_ld.offset, _abi.LrlRolloutStore.hist_ld.offset,
-                   C.sizeof(_abi.LrlDevCurriculum), _abi.LrlDevCurriculum.nz.offset, _abi.LrlDevCurriculum.draws.offset]
+                   C.sizeof(_abi.LrlDevCurriculum), _abi.LrlDevCurriculum.nz.offset, _abi.LrlDevCurriculum.draws.offset, C.sizeof(_abi.LrlGemmDesc), _abi.LrlGemmDesc.splits.offset,
+                   _abi.LrlGemmDesc.A.offset, _abi.LrlGemmDesc.lda.offset, _abi.LrlGemmDesc.workspace_floats.offset,
+                   _abi.LrlGemmDesc.splits_out.offset]
 
 
 def test_product_fails_loudly_without_gpu():

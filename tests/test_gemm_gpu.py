@@ -1,8 +1,13 @@
 """fp32 MFMA GEMM of the native PPO update (csrc/lrl_gemm.hip, through lrl_gemm_f32) against a plain
 torch fp32 reference of the same op: the three layouts an MLP's forward / backward-data / weight-gradient
-need, every epilogue, gathered rows, ragged and unaligned shapes; the 64-aligned float4 shapes take the
-LDS-DMA kernel, outputs <= 32 wide with k = 512 / 1024 the thin kernel (B in registers), the others the
-register-staged one."""
+need, every epilogue, gathered rows, ragged and unaligned shapes, all contiguous and in one group.  With the default
+switches the forward / backward-data shapes with n >= 16, m >= 64, k >= 32 run on the split-bf16 kernel
+(gemm_x6_kernel, 64 x 64 tiles here), outputs <= 32 wide with k = 512 / 1024 and m >= 256 on the 16-row thin kernel
+(B in registers), the rest (n < 16, k < 32) on the register-staged fp32 kernel; the weight gradients with m a multiple
+of 128 and whole n tiles inside the row pitch run on gemm_x6t_kernel, the others with m, n >= 16 on gemm_x6_kernel,
+(12, 128, 96) on the register-staged one.  The fp32 LDS-DMA kernels (glds, glds32, glds_tn) and the 32-row thin kernel
+are not reached from here; tests/test_gemm_forms_gpu.py runs every family, asserts which one ran, and covers the
+grouped / pitched operand forms."""
 import ctypes as C
 
 import numpy as np
