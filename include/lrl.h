@@ -22,6 +22,7 @@
  *                          ~ gym.set_actor_root_state_tensor_indexed / set_dof_state_tensor_indexed
  *                            (legged_robot.py:303-312, 710-712, 739-741)
  *   lrl_sim_refresh_rigid_body_state ~ gym.refresh_rigid_body_state_tensor (:147)
+ *   lrl_sim_render / lrl_sim_record ~ the env-0 camera sensor and the video-frame lists (:1301-1355, 743-755)
  *   lrl_gae                ~ RolloutStorage.compute_returns (rollout_storage.py:76-90)
  *   lrl_ppo_act            ~ PPO.act teacher path (ppo.py:62-74 -> actor_critic.py:137-147,170-173)
  *                            fused with RolloutStorage.add_transitions (rollout_storage.py:57-71)
@@ -439,6 +440,72 @@ int32_t lrl_sim_set_terrain(lrl_sim* sim, const float* vertices, const int16_t* 
                             int32_t cols);
 /* HistoryWrapper.get_observations side effect (history_wrapper.py:26-30) */
 int32_t lrl_sim_shift_history(lrl_sim* sim, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Headless camera (gym.create_camera_sensor / render_all_camera_sensors / get_camera_image IMAGE_COLOR,
+ * legged_robot.py:1301-1355): a ray caster over the sim's own collision model, one env per call.  What is drawn: the
+ * base box (the span of the base's collision shapes), every collision sphere with a radius, and one capsule of radius
+ * LRL_RENDER_LINK_RADIUS per leg link (hip origin -> thigh origin, thigh origin -> calf origin, calf origin -> the centre
+ * of the leg's calf / foot sphere with a radius that lies farthest from the calf origin); the ground plane z = 0 or the
+ * terrain mesh of lrl_sim_set_terrain (nothing outside its grid).  Visual meshes and the hull support tables are not
+ * drawn.
+ *   camera: f = normalize(target - pos), r = normalize(f x z) (f x y when |f x z| < 1e-6), up = r x f; pixel (row i from
+ *   the top, column j) looks along normalize(f + u r + v up), u = (2 (j + 1/2) / W - 1) tan(hfov / 2),
+ *   v = (1 - 2 (i + 1/2) / H) tan(hfov / 2) H / W; rays end at `far`.
+ *   shading: channel = round(255 clamp(albedo (ambient + (1 - ambient) max(0, n . l) lit))), lit = 0 when a ray from
+ *   the hit point + 1e-3 n towards the light meets one of the robot's primitives; the ground's albedo is a 1 m
+ *   checkerboard in world xy ((floor(x) + floor(y)) odd: LRL_RENDER_GROUND_B).
+ * ------------------------------------------------------------------------------------------ */
+#define LRL_RENDER_LINK_RADIUS 0.02f
+#define LRL_RENDER_LIGHT_X 0.35f /* direction towards the light (normalised by its users) */
+#define LRL_RENDER_LIGHT_Y -0.45f
+#define LRL_RENDER_LIGHT_Z 0.82f
+#define LRL_RENDER_AMBIENT 0.35f
+#define LRL_RENDER_SKY_R 0.55f
+#define LRL_RENDER_SKY_G 0.70f
+#define LRL_RENDER_SKY_B 0.90f
+#define LRL_RENDER_GROUND_A_R 0.80f
+#define LRL_RENDER_GROUND_A_G 0.80f
+#define LRL_RENDER_GROUND_A_B 0.78f
+#define LRL_RENDER_GROUND_B_R 0.45f
+#define LRL_RENDER_GROUND_B_G 0.47f
+#define LRL_RENDER_GROUND_B_B 0.50f
+#define LRL_RENDER_BASE_R 0.85f
+#define LRL_RENDER_BASE_G 0.30f
+#define LRL_RENDER_BASE_B 0.20f
+#define LRL_RENDER_SPHERE_R 0.95f
+#define LRL_RENDER_SPHERE_G 0.75f
+#define LRL_RENDER_SPHERE_B 0.15f
+#define LRL_RENDER_LINK_R 0.20f
+#define LRL_RENDER_LINK_G 0.35f
+#define LRL_RENDER_LINK_B 0.80f
+
+#define LRL_CAM_FOLLOW 1u /* pos / target are offsets from the env's base position (read on the device) */
+typedef struct lrl_camera {
+  float pos[3], target[3]; /* world frame; with LRL_CAM_FOLLOW: offsets added to the env's base position */
+  float hfov_deg, far;     /* Isaac Gym's CameraProperties default: 90 degrees */
+  int32_t width, height;
+  uint32_t flags;
+} lrl_camera;
+/* ids of the `ids` image: 0 nothing, 1 ground, 2 base box, 3 + s sphere s (model order),
+ * 3 + LRL_MAX_SPHERES + 3 leg + link a link capsule; | LRL_RENDER_ID_SHADOW when the hit point is in shadow */
+#define LRL_RENDER_ID_SHADOW 0x10000
+/* One image of env `env` from the sim's current state: refreshes the rigid-body state on `stream` (LRL_T_RIGID_BODY_STATE
+ * is valid afterwards), then one thread per pixel.  Device outputs: rgba uint8 [height][width][4] (alpha 255), and, each
+ * optional (NULL), depth f32 [height][width] (distance along the ray, +inf where nothing is hit) and ids int32
+ * [height][width].  LRL_E_INVALID, with a message and no launch: env outside [0, n), width / height outside [1, 4096],
+ * hfov_deg outside (1, 179), far <= 0, a null camera or rgba. */
+int32_t lrl_sim_render(lrl_sim* sim, int32_t env, const lrl_camera* cam, uint8_t* rgba, float* depth, int32_t* ids,
+                       void* stream);
+/* The reference's recording state machine (legged_robot.py:743-748, 1332-1340) without a host round trip: one call per
+ * env step, after the step's resets.  A one-thread kernel reads env's reset flag (LRL_T_RESET) and advances `state`
+ * (device int32 [3]: phase, count, slot; zero-initialised by the caller): phase 0 waits for the env's first reset (-> 1
+ * on a reset, -> 3 "gave up" after `capacity` calls without one), phase 1 records (-> 2 "complete" on the next reset or
+ * when count == capacity).  In phase 1 slot = count++ and the image is rendered into ring[slot] (ring: uint8
+ * [capacity][height][width][4]); otherwise slot = -1 and the render kernel returns at once.  A complete video is
+ * ring[0 .. count): the frames from the first reset's step to the last step before the next reset. */
+int32_t lrl_sim_record(lrl_sim* sim, int32_t env, const lrl_camera* cam, uint8_t* ring, int32_t capacity,
+                       int32_t* state, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * PPO numeric core.

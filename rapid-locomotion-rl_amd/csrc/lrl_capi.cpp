@@ -54,6 +54,9 @@ hipError_t lrl_launch_shift_history(const KState*, int, int, int, hipStream_t);
 hipError_t lrl_launch_garbage(uint32_t mode, uint32_t pat, hipStream_t st);
 hipError_t lrl_launch_randomize(const KState*, const float*, const float*, const float*, const float*, uint32_t,
                                 hipStream_t);
+hipError_t lrl_launch_render(const KParams*, const KState*, const KRender*, const lrl_camera*, int32_t, uint8_t*, float*,
+                             int32_t*, const int32_t*, hipStream_t);
+hipError_t lrl_launch_record_state(const KState*, int32_t, int32_t, int32_t*, hipStream_t);
 }
 
 struct lrl_sim {
@@ -78,7 +81,47 @@ struct lrl_sim {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
   size_t ev_used = 0;
   uint32_t garbage_mode = 0, garbage_pat = 0;  // lrl_debug_sim_garbage
+  KRender rt;  // lrl_sim_render's model tables
 };
+
+// What the camera draws of the model (include/lrl.h): the pose body of every sphere with a radius, and the end points
+// of the 12 link capsules.
+static void render_tables(const lrl_model* m, KRender* t) {
+  int body[LRL_NUM_LEGS][3];
+  for (int l = 0; l < LRL_NUM_LEGS; ++l)
+    for (int k = 0; k < 3; ++k) body[l][k] = -1;
+  for (int b = 0; b < m->num_bodies; ++b) {
+    const int l = m->body_leg[b], k = m->body_link[b];
+    if (l >= 0 && l < LRL_NUM_LEGS && k >= 0 && k < 3 && body[l][k] < 0) body[l][k] = b;
+  }
+  for (int s = 0; s < LRL_MAX_SPHERES; ++s) {
+    t->sph_body[s] = -1;
+    if (s >= m->num_spheres || !(m->sphere_radius[s] > 0.f)) continue;
+    const int b = m->sphere_body[s], l = m->body_leg[b];
+    // a fixed foot's spheres are expressed in the calf frame (lrl/robot.py)
+    t->sph_body[s] = (l >= 0 && l < LRL_NUM_LEGS && m->body_link[b] > 2) ? body[l][2] : b;
+  }
+  for (int l = 0; l < LRL_NUM_LEGS; ++l)
+    for (int k = 0; k < 3; ++k) {
+      const int c = 3 * l + k;
+      t->cap_a[c] = body[l][k];
+      t->cap_b[c] = k < 2 ? body[l][k + 1] : -1;
+      t->cap_sph[c] = -1;
+      if (k < 2) {
+        if (t->cap_b[c] < 0) t->cap_a[c] = -1;
+        continue;
+      }
+      float far2 = -1.f;  // the calf's (or its fixed foot's) sphere farthest from the calf origin, the first on a tie
+      for (int s = 0; s < m->num_spheres; ++s) {
+        const int b = m->sphere_body[s];
+        if (m->body_leg[b] != l || m->body_link[b] < 2 || t->sph_body[s] < 0) continue;
+        const float* q = m->sphere_pos[s];
+        const float d2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2];
+        if (d2 > far2) { far2 = d2; t->cap_sph[c] = s; }
+      }
+      if (t->cap_sph[c] < 0) t->cap_a[c] = -1;
+    }
+}
 
 static void quat_to_rowmajor(const float* q, float* R) {
   float x = q[0], y = q[1], z = q[2], w = q[3];
@@ -287,6 +330,7 @@ int32_t lrl_sim_create(const lrl_model* model, const lrl_env_params* params, int
   s->device = device;
   int rc = digest(model, params, &s->hk);
   if (rc) { delete s; return rc; }
+  render_tables(model, &s->rt);
   HIPCHECK(hipSetDevice(device));
   const int n = num_envs, N = (n + 63) / 64 * 64;
   const int B = model->num_bodies, NO = params->num_obs, H = params->num_history * NO;
@@ -761,6 +805,39 @@ int32_t lrl_sim_extras_snapshot(lrl_sim* s, float* out, void* stream) {
 int32_t lrl_sim_refresh_rigid_body_state(lrl_sim* s, void* stream) {
   if (!s) return fail(LRL_E_INVALID, "null sim");
   HIPCHECK(lrl_launch_rigid_body(s->dk, &s->S, s->d_body_leg, s->d_body_link, s->d_foot_xyz, (hipStream_t)stream));
+  return 0;
+}
+
+static int render_args(lrl_sim* s, int32_t env, const lrl_camera* cam, const void* out) {
+  if (!s) return fail(LRL_E_INVALID, "null sim");
+  if (!cam) return fail(LRL_E_INVALID, "null camera");
+  if (!out) return fail(LRL_E_INVALID, "null image buffer");
+  if (env < 0 || env >= s->S.n) return fail(LRL_E_INVALID, "env %d of %d", env, s->S.n);
+  if (cam->width < 1 || cam->width > 4096 || cam->height < 1 || cam->height > 4096)
+    return fail(LRL_E_INVALID, "image size %d x %d outside [1, 4096]", cam->width, cam->height);
+  if (!(cam->hfov_deg > 1.f && cam->hfov_deg < 179.f)) return fail(LRL_E_INVALID, "hfov_deg %g outside (1, 179)", cam->hfov_deg);
+  if (!(cam->far > 0.f) || !(cam->far < 3.0e38f)) return fail(LRL_E_INVALID, "far %g", cam->far);
+  if (s->hk.p.terrain_mesh && !s->hk.terr_vtx) return fail(LRL_E_INVALID, "terrain_mesh set but no lrl_sim_set_terrain");
+  return 0;
+}
+
+int32_t lrl_sim_render(lrl_sim* s, int32_t env, const lrl_camera* cam, uint8_t* rgba, float* depth, int32_t* ids,
+                       void* stream) {
+  const int rc = render_args(s, env, cam, rgba);
+  if (rc) return rc;
+  HIPCHECK(lrl_launch_rigid_body(s->dk, &s->S, s->d_body_leg, s->d_body_link, s->d_foot_xyz, (hipStream_t)stream));
+  HIPCHECK(lrl_launch_render(s->dk, &s->S, &s->rt, cam, env, rgba, depth, ids, nullptr, (hipStream_t)stream));
+  return 0;
+}
+
+int32_t lrl_sim_record(lrl_sim* s, int32_t env, const lrl_camera* cam, uint8_t* ring, int32_t capacity, int32_t* state,
+                       void* stream) {
+  const int rc = render_args(s, env, cam, ring);
+  if (rc) return rc;
+  if (capacity < 1 || !state) return fail(LRL_E_INVALID, "lrl_sim_record: capacity %d, state %p", capacity, (void*)state);
+  HIPCHECK(lrl_launch_record_state(&s->S, env, capacity, state, (hipStream_t)stream));
+  HIPCHECK(lrl_launch_rigid_body(s->dk, &s->S, s->d_body_leg, s->d_body_link, s->d_foot_xyz, (hipStream_t)stream));
+  HIPCHECK(lrl_launch_render(s->dk, &s->S, &s->rt, cam, env, ring, nullptr, nullptr, state + 2, (hipStream_t)stream));
   return 0;
 }
 

@@ -79,6 +79,16 @@ struct KParams {
   uint32_t* self_stats;
 };
 
+// lrl_sim_render's view of the model (lrl_render.hip), built by lrl_sim_create and passed to the kernel by value
+struct KRender {
+  // body whose pose (rigid-body state) carries sphere s: its owner, or for a fixed foot's spheres the calf they are
+  // expressed in (lrl/robot.py); -1 = not drawn (radius 0)
+  int32_t sph_body[LRL_MAX_SPHERES];
+  // capsule 3 leg + link: body at end a (-1: no capsule), body at end b, or (calf capsules: cap_b = -1) the sphere
+  // whose centre is end b
+  int32_t cap_a[3 * LRL_NUM_LEGS], cap_b[3 * LRL_NUM_LEGS], cap_sph[3 * LRL_NUM_LEGS];
+};
+
 // SoA device buffers of a sim (each [.][N] with N = padded env count unless noted).
 struct KState {
   int32_t n;       // real env count

@@ -134,6 +134,26 @@ GEMM_FAMILIES = {1: "x6p", 2: "x6t", 3: "x6", 4: "x6d", 5: "glds", 6: "glds32", 
                  9: "thin32", 10: "staged"}
 
 
+class LrlCamera(C.Structure):
+    """lrl_camera (lrl_sim_render / lrl_sim_record)."""
+    _fields_ = [("pos", f32 * 3), ("target", f32 * 3), ("hfov_deg", f32), ("far", f32), ("width", i32),
+                ("height", i32), ("flags", u32)]
+
+
+# the camera's constants (the LRL_RENDER_* / LRL_CAM_* defines of include/lrl.h; tests/test_render_abi.py compares)
+CAM_FOLLOW = 1
+RENDER_ID_SHADOW = 0x10000
+RENDER_LINK_RADIUS = 0.02
+RENDER_LIGHT = (0.35, -0.45, 0.82)  # towards the light, normalised by its users
+RENDER_AMBIENT = 0.35
+RENDER_SKY = (0.55, 0.70, 0.90)
+RENDER_GROUND_A = (0.80, 0.80, 0.78)
+RENDER_GROUND_B = (0.45, 0.47, 0.50)
+RENDER_BASE = (0.85, 0.30, 0.20)
+RENDER_SPHERE = (0.95, 0.75, 0.15)
+RENDER_LINK = (0.20, 0.35, 0.80)
+
+
 PPO_CTRL_BYTES = 64  # sizeof(lrl_ppo_ctrl): double lr, double loss_sum[3], float mb[4], float x4
 
 
@@ -161,7 +181,7 @@ _lib = None
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 # the files and order of csrc/Makefile's SRC_HASH (SRCS then HDRS)
 _HASHED = ["lrl_env.hip", "lrl_aux.hip", "lrl_gae.hip", "lrl_gemm.hip", "lrl_ppo.hip", "lrl_capi.cpp", "lrl_curriculum.cpp",
-           "lrl_curriculum_dev.hip", "lrl_env_flat.hip", "lrl_kparams.h", "lrl_gemm.h", "../../include/lrl.h", "../../include/lrl_philox.h",
+           "lrl_curriculum_dev.hip", "lrl_env_flat.hip", "lrl_render.hip", "lrl_kparams.h", "lrl_gemm.h", "../../include/lrl.h", "../../include/lrl_philox.h",
            "Makefile"]  # (the build flags too: a library built with other flags is stale)
 
 
@@ -203,7 +223,7 @@ def lib():
                      "lrl_sim_apply_commands", "lrl_sim_extras_snapshot", "lrl_sim_env_lists",
                      "lrl_sim_terrain_curriculum_dev", "lrl_sim_reset_idx_dev", "lrl_sim_observe_idx_dev",
                      "lrl_rows_mean_zero_dev", "lrl_sim_curriculum_resample_dev", "lrl_debug_gemm_paths",
-                     "lrl_debug_sim_garbage", "lrl_debug_sim_arena"]:
+                     "lrl_debug_sim_garbage", "lrl_debug_sim_arena", "lrl_sim_render", "lrl_sim_record"]:
             getattr(L, name).restype = C.c_int32
         L.lrl_np_sum_f64.restype = C.c_double
         L.lrl_np_sum_f64.argtypes = [C.c_void_p, C.c_int64]

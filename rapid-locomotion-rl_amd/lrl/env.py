@@ -351,8 +351,14 @@ class LeggedRobotEnv:
             self.height_points[:, :, :2] = torch.tensor(lparams.height_points(cfg), device=self.device)
         self.common_step_counter = 0
         self.extras = _LazyExtras(self)
+        # headless camera (legged_robot.py:1301-1319): env 0's, and the first eval env's, 360 x 240 follow camera
         self.record_now = False
-        self.complete_video_frames = []
+        self.record_eval_now = False
+        self.video_capacity = None  # frames a video may hold (None: one full episode, max_episode_length + 1)
+        self._rec = {}              # "train" / "eval" -> the recording in progress (ring, state), see start_recording
+        if cfg.env.record_video:
+            # (horizontal_fov: gymapi.CameraProperties' default; far_plane bounds the ray caster's reach)
+            self.camera_props = Section(width=360, height=240, horizontal_fov=90.0, far_plane=100.0)
 
         # ---- origins, DR draws at creation (legged_robot.py:1216-1231, 1385-1415, 519-542) ----
         self._set_env_origins()
@@ -746,6 +752,10 @@ class LeggedRobotEnv:
         self._register_extras(ex)
         if tm is not None:
             tm.mark("extras")
+        if self.record_now:  # _render_headless (legged_robot.py:148, 1332-1355), after the step's resets
+            self._record_frame("train")
+        if self.record_eval_now:
+            self._record_frame("eval")
         return self.obs_buf, self.rew_buf, self._reset_u8.view(torch.bool), self.extras
 
     # rows of lrl_sim_extras_snapshot (include/lrl.h LRL_EXTRAS_*): key -> (first row, rows)
@@ -895,6 +905,8 @@ class LeggedRobotEnv:
         ex["privileged_obs"] = self.privileged_obs_buf
         ex["joint_vel_target"] = torch.zeros(12)
         self._register_extras(ex)
+        if self.record_now:  # (record_eval_now: this path has no eval group)
+            self._record_frame("train")
         return self.obs_buf, self.rew_buf, self._reset_u8.view(torch.bool), self.extras
 
     def kernel_timing(self, start):
@@ -930,10 +942,42 @@ class LeggedRobotEnv:
     def get_privileged_observations(self, horizon=0):
         return self.privileged_obs_buf
 
+    def _camera(self, width=None, height=None, offset=(0.0, -1.0, 1.0), target=(0.0, 0.0, 0.0), follow=True, hfov=None,
+                far=None):
+        """An lrl_camera: by default the reference's follow camera (legged_robot.py:1323-1325: at base + (0, -1, 1),
+        looking at the base) with the camera sensor's properties."""
+        cp = self.camera_props
+        cam = _abi.LrlCamera()
+        cam.pos[:] = [float(x) for x in offset]
+        cam.target[:] = [float(x) for x in target]
+        cam.hfov_deg = float(cp.horizontal_fov if hfov is None else hfov)
+        cam.far = float(cp.far_plane if far is None else far)
+        cam.width = int(cp.width if width is None else width)
+        cam.height = int(cp.height if height is None else height)
+        cam.flags = _abi.CAM_FOLLOW if follow else 0
+        return cam
+
+    def render_images(self, env_id=0, camera=None, depth=False, ids=False):
+        """One image of env `env_id` from the current state through liblrl's ray caster (lrl_sim_render; the collision
+        model plus link capsules): device tensors (rgba uint8 [H, W, 4], depth f32 [H, W] or None, ids int32
+        [H, W] or None)."""
+        if not hasattr(self, "camera_props"):
+            raise RuntimeError("no camera: cfg.env.record_video is off")
+        cam = self._camera() if camera is None else camera
+        h, w = max(int(cam.height), 0), max(int(cam.width), 0)
+        rgba = torch.empty(h, w, 4, dtype=torch.uint8, device=self.device)
+        dep = torch.empty(h, w, dtype=torch.float32, device=self.device) if depth else None
+        idt = torch.empty(h, w, dtype=torch.int32, device=self.device) if ids else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _abi.check(self._L.lrl_sim_render(self._sim, C.c_int32(env_id), C.byref(cam), ptr(rgba), ptr(dep), ptr(idt),
+                                          self._stream()))
+        return rgba, dep, idt
+
     def render(self, mode="rgb_array"):
-        """BaseTask.render (base_task.py:92-118) draws through the Isaac Gym viewer / camera sensors; rendering is out of
-        scope here (no viewer), so asking for a frame is an error, not a blank image."""
-        raise NotImplementedError("no viewer / camera rendering in this framework (DESIGN.md §8)")
+        """LeggedRobot.render (legged_robot.py:1321-1330): env 0 seen from its follow camera, a numpy uint8
+        (height, width, 4) image (the camera sensor's IMAGE_COLOR)."""
+        assert mode == "rgb_array"
+        return self.render_images(0)[0].cpu().numpy()
 
     def reset(self):
         """VelocityTrackingEasyEnv.reset (:66-69): reset all, then one zero-action step."""
@@ -1177,24 +1221,78 @@ class LeggedRobotEnv:
     def shift_history(self):
         _abi.check(self._L.lrl_sim_shift_history(self._sim, self._stream()))
 
-    # ---- recording hooks used by Runner.log_video (rendering is out of scope) ----
+    # ---- recording hooks used by Runner.log_video (legged_robot.py:743-755, 1332-1383) ----
+    # A video is one full episode of the env: the frames from the step of its first reset after start_recording to the
+    # last step before its next reset.  The frames stay on the device (lrl_sim_record: a ring of `capacity` frames and
+    # a 3-word state, no host round trip per step); a video longer than the ring closes at its capacity, and an env
+    # that does not reset within `capacity` steps gives the recording up (the fork's steps never reset).
+    def _start_recording(self, key, env_id):
+        if not hasattr(self, "camera_props"):
+            raise RuntimeError("no camera: cfg.env.record_video is off")
+        cap = int(self.video_capacity) if self.video_capacity else int(self.max_episode_length) + 1
+        r = self._rec.get(key)
+        if r is None or r["capacity"] != cap:
+            cp = self.camera_props
+            r = self._rec[key] = dict(env=env_id, capacity=cap, camera=self._camera(), ring=torch.empty(
+                cap, cp.height, cp.width, 4, dtype=torch.uint8, device=self.device))
+        r["state"] = torch.zeros(3, dtype=torch.int32, device=self.device)  # phase, count, slot
+        r["frames"] = None
+
+    def _record_frame(self, key):
+        r = self._rec.get(key)
+        if r is not None:
+            _abi.check(self._L.lrl_sim_record(self._sim, C.c_int32(r["env"]), C.byref(r["camera"]),
+                                              C.c_void_p(r["ring"].data_ptr()), C.c_int32(r["capacity"]),
+                                              C.c_void_p(r["state"].data_ptr()), self._stream()))
+
+    def _complete_frames(self, key):
+        """The finished video as a list of numpy frames, [] while it is not complete; the second value tells that the
+        recording gave up."""
+        r = self._rec.get(key)
+        if r is None:
+            return [], False
+        if r["frames"] is None:
+            phase, count, _ = r["state"].cpu().tolist()  # (12 bytes: the one read-back while recording)
+            if phase == 3:
+                return [], True
+            if phase != 2:
+                return [], False
+            r["frames"] = list(r["ring"][:count].cpu().numpy())
+        return r["frames"], False
+
+    # start_recording while a recording runs (or waits to be fetched) leaves it alone: a Runner whose
+    # save_video_interval is shorter than an episode would otherwise restart it every time and never finish one (the
+    # reference drops the finished frames there and keeps appending).
     def start_recording(self):
+        if not (self.record_now and "train" in self._rec):
+            self._start_recording("train", 0)
         self.record_now = True
 
     def start_recording_eval(self):
-        pass
+        if self.eval_cfg is not None:
+            if not (self.record_eval_now and "eval" in self._rec):
+                self._start_recording("eval", self.num_train_envs)
+            self.record_eval_now = True
 
     def pause_recording(self):
+        self._rec.pop("train", None)  # frees the ring
         self.record_now = False
 
     def pause_recording_eval(self):
-        pass
+        self._rec.pop("eval", None)
+        self.record_eval_now = False
 
     def get_complete_frames(self):
-        return []
+        frames, gave_up = self._complete_frames("train")
+        if gave_up:
+            self.pause_recording()
+        return frames
 
     def get_complete_frames_eval(self):
-        return []
+        frames, gave_up = self._complete_frames("eval")
+        if gave_up:
+            self.pause_recording_eval()
+        return frames
 
 
 VelocityTrackingEasyEnv = LeggedRobotEnv

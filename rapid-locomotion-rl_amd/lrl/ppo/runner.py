@@ -103,6 +103,8 @@ class Runner:
             mv, ms, ma = self.alg.update()
             lg.store_metrics(time_elapsed=lg.since("start"), time_iter=lg.split("epoch"), adaptation_loss=ma,
                              mean_value_loss=mv, mean_surrogate_loss=ms)
+            if self.args.save_video_interval:
+                self.log_video(it)
             self.tot_timesteps += self.num_steps_per_env * self.env.num_envs
             if lg.every(self.args.log_freq, "iteration", start_on=1):
                 lg.log_metrics_summary(key_values={"timesteps": self.tot_timesteps, "iterations": it})
@@ -112,6 +114,29 @@ class Runner:
         self.current_learning_iteration += num_learning_iterations
         if num_learning_iterations > 0:  # the reference always saves after the loop (__init__.py:246-265)
             self.save(tot_iter - 1)
+
+    def log_video(self, it):
+        """__init__.py:267-286: every save_video_interval iterations start recording env 0 (and the first eval env), and
+        save a video once a full episode of it is complete (videos/{it:05d}.mp4 in the reference; the logger keeps the
+        frames as .npz, and a .gif when it can).  An env without a camera (lrl.hlp's wrapper, record_video off) logs none."""
+        env = self.env
+        if not hasattr(env, "start_recording") or not hasattr(env, "camera_props"):
+            return
+        lg = self.logger
+        if it - self.last_recording_it >= self.args.save_video_interval:
+            env.start_recording()
+            if env.num_eval_envs > 0:
+                env.start_recording_eval()
+            self.last_recording_it = it
+        frames = env.get_complete_frames()
+        if len(frames) > 0:
+            env.pause_recording()
+            lg.save_video(frames, f"videos/{it:05d}.mp4", fps=1 / env.dt)
+        if env.num_eval_envs > 0:
+            frames = env.get_complete_frames_eval()
+            if len(frames) > 0:
+                env.pause_recording_eval()
+                lg.save_video(frames, f"videos/{it:05d}_eval.mp4", fps=1 / env.dt)
 
     def _eval_actions(self, obs, priv, hist, n_train, eval_expert):
         ac = self.alg.actor_critic

@@ -145,11 +145,21 @@ class ML_Logger:
             shutil.copyfile(file_path, d)
 
     def save_video(self, frames, key, fps=None, **_):
-        """No video encoder in this image: the frames are kept as an ``.npz`` (frames [T, H, W, C], fps) next to
-        where the reference's mp4 would go."""
+        """No mp4 encoder here: the frames are kept as an ``.npz`` (frames [T, H, W, C], fps) next to where the
+        reference's mp4 would go, and, when PIL is installed, as an animated ``.gif`` beside it."""
         p = self._path(os.path.splitext(key)[0] + ".npz")
-        if p is not None and len(frames):
-            np.savez_compressed(p, frames=np.stack([np.asarray(f) for f in frames]), fps=np.float64(fps or 0.0))
+        if p is None or not len(frames):
+            return
+        arr = np.stack([np.asarray(f) for f in frames])
+        np.savez_compressed(p, frames=arr, fps=np.float64(fps or 0.0))
+        try:
+            from PIL import Image
+        except ImportError:
+            return
+        if arr.dtype == np.uint8 and arr.ndim == 4 and arr.shape[-1] in (3, 4):
+            imgs = [Image.fromarray(a[..., :3]) for a in arr]
+            imgs[0].save(os.path.splitext(p)[0] + ".gif", save_all=True, append_images=imgs[1:], loop=0,
+                         duration=int(round(1000.0 / fps)) if fps else 40)
 
     # ---- timers ----
     def start(self, *keys):

@@ -6,9 +6,10 @@ Cheetah, the robot that run used).  The env is the evaluation env of load_env (d
 terrain tiles, no border); the policy is act_inference = the adaptation module on the observation history +
 the actor (``ActorCritic.act_student_fused``, the native GEMM chain).  A constant forward command is tracked for
 ``--steps`` policy steps after 20 zero-action steps, as play_mc does; the measured forward velocity is printed
-(and plotted with ``--plot out.png``).  Rendering is out of scope.
+(and plotted with ``--plot out.png``).  ``--video OUT`` writes one frame of env 0 per policy step (the headless
+camera of ``env.render()``: the collision model plus link capsules) as ``OUT.npz``, and ``OUT.gif`` when PIL is installed.
 
-  python scripts/play.py [--robot mc|go1] [--weights ac_weights.pt] [--envs 64] [--steps 1000] [--vx 1.0]
+  python scripts/play.py [--robot mc|go1] [--weights ac_weights.pt] [--envs 64] [--steps 1000] [--vx 1.0] [--video OUT]
 """
 import argparse
 import json
@@ -55,7 +56,8 @@ def load_policy(weights, cfg, device):
     return lambda ob: ac.act_student_fused(ob["obs"].contiguous(), ob["obs_history"])[0]
 
 
-def play(robot="mc", weights=None, num_envs=64, steps=1000, vx=1.0, vy=0.0, wz=0.0, device="cuda:0"):
+def play(robot="mc", weights=None, num_envs=64, steps=1000, vx=1.0, vy=0.0, wz=0.0, device="cuda:0", frames=None):
+    """``frames``: a list that receives env 0's rendered frame (numpy uint8 [240, 360, 4]) after every policy step."""
     env, cfg = load_env(robot, num_envs, device)
     policy = load_policy(weights, cfg, device)
     e = env.env
@@ -78,6 +80,8 @@ def play(robot="mc", weights=None, num_envs=64, steps=1000, vx=1.0, vy=0.0, wz=0
         obs, rew, done, info = env.step(actions)
         vel[i, :, :2] = e.base_lin_vel[:, :2].cpu().numpy()
         vel[i, :, 2] = e.base_ang_vel[:, 2].cpu().numpy()
+        if frames is not None:
+            frames.append(e.render())
     upright = (e.projected_gravity[:, 2] < -0.8).float().mean().item()
     e.close()
     return vel, upright, e.dt
@@ -91,8 +95,14 @@ def main():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--vx", type=float, default=1.0)
     ap.add_argument("--plot", default=None)
+    ap.add_argument("--video", default=None, metavar="OUT", help="write env 0's frames to OUT.npz (and OUT.gif)")
     a = ap.parse_args()
-    vel, upright, dt = play(a.robot, a.weights, a.envs, a.steps, a.vx)
+    frames = [] if a.video else None
+    vel, upright, dt = play(a.robot, a.weights, a.envs, a.steps, a.vx, frames=frames)
+    if a.video:
+        from ml_logger import ML_Logger
+        out = os.path.abspath(os.path.splitext(a.video)[0])
+        ML_Logger().configure(os.path.dirname(out)).save_video(frames, os.path.basename(out) + ".mp4", fps=1 / dt)
     tail = vel[len(vel) // 2:]
     print(json.dumps({"robot": a.robot, "command_vx": a.vx, "steps": a.steps, "envs": a.envs,
                       "measured_vx_mean": round(float(tail[..., 0].mean()), 4),
