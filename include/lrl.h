@@ -214,6 +214,13 @@ typedef struct lrl_env_params {
    * iterations sweep the whole sub-step with the start targets.  Plane ground only (the terrain-mesh build solves
    * with PGS and the host passes 0 there). */
   int32_t solver_tgs;
+  /* observation-layout switches (compute_observations :342-417; all 0 = the layout above):
+   * observe_only_ang_vel / observe_only_lin_vel (Cfg.env, :370-376): base-frame angular / linear velocity x scale in
+   * front of the row, the linear block first;  observe_yaw (:378-383): one entry clip(0.5 wrap_to_pi(heading), -1, 1)
+   * after the actions and before the height rows, heading = atan2 of quat_apply(base_quat, x);
+   * global_reference (Cfg.commands, :361-364, :1580-1581): the observe_vel linear block and the tracking_lin_vel
+   * error read root_states[:, 7:10] (world frame, after _push_robots) instead of base_lin_vel. */
+  int32_t observe_only_ang_vel, observe_only_lin_vel, observe_yaw, global_reference;
 } lrl_env_params;
 
 /* ------------------------------------------------------------------------------------------

@@ -224,6 +224,7 @@ static int digest(const lrl_model* m, const lrl_env_params* p, KParams* k) {
     return fail(LRL_E_INVALID, "num_height_points %d", p->num_height_points);
   if (p->terrain_mesh && p->horizontal_scale <= 0.f) return fail(LRL_E_INVALID, "horizontal_scale");
   int obs_expected = 3 + (p->observe_command ? 3 : 0) + 36 + (p->observe_vel ? 6 : 0) +
+                     (p->observe_only_lin_vel ? 3 : 0) + (p->observe_only_ang_vel ? 3 : 0) + (p->observe_yaw ? 1 : 0) +
                      (p->measure_heights ? p->num_height_points : 0);
   if (obs_expected != p->num_obs) return fail(LRL_E_INVALID, "obs layout %d != num_obs %d", obs_expected, p->num_obs);
   for (int l = 0; l < 4; ++l)

@@ -2169,15 +2169,47 @@ __device__ __forceinline__ float height_sample(const KParams* __restrict__ K, co
 // the fused step kernel
 // ------------------------------------------------------------------------------------------------
 // compute_observations (legged_robot.py:342-417) in two parts: the row's values — obs_base_values writes its base
-// entries ([lin vel, ang vel,] gravity, [commands]), the step kernel's quads write the dof positions / velocities and the
-// actions after them (each lane its leg's joints) — then obs_noise_clip adds U[-1,1] x noise_vec from the counter RNG
-// keyed by (env, step counter, 4-entry chunk) and clips, for chunks c0, c0 + cstep, ... (the step kernel spreads the
-// chunks over an env's lanes; a re-evaluation after a reset draws the same noise)
+// entries ([only lin vel,] [only ang vel,] [lin vel, ang vel,] gravity, [commands]) and the yaw entry, the step kernel's
+// quads write the dof positions / velocities and the actions between them (each lane its leg's joints) — then
+// obs_noise_clip adds U[-1,1] x noise_vec from the counter RNG keyed by (env, step counter, 4-entry chunk) and clips,
+// for chunks c0, c0 + cstep, ... (the step kernel spreads the chunks over an env's lanes; a re-evaluation after a
+// reset draws the same noise)
+// number of base entries = offset of the dof positions in the row (uniform: P's switches only)
+__device__ __forceinline__ int obs_joint_offset(const lrl_env_params& P) {
+  return (P.observe_only_lin_vel ? 3 : 0) + (P.observe_only_ang_vel ? 3 : 0) + (P.observe_vel ? 6 : 0) + 3 +
+         (P.observe_command ? 3 : 0);
+}
+// observe_yaw's entry (:378-383): forward = quat_apply(base_quat, [1, 0, 0]) (torch_utils: t = cross(xyz, b) * 2,
+// b + w t + cross(xyz, t), the products with b's zeros kept in torch's order), heading = atan2(forward.y, forward.x),
+// wrap_to_pi (math_utils.py:20-23: python-style remainder by float32(2 pi), minus float32(2 pi) above float32(pi)),
+// halved and clipped to [-1, 1]
+__device__ __forceinline__ float obs_yaw_value(const float* q) {
+  const float x = q[0], y = q[1], z = q[2], w = q[3];
+  const float t0 = (y * 0.f - z * 0.f) * 2.f, t1 = (z * 1.f - x * 0.f) * 2.f, t2 = (x * 0.f - y * 1.f) * 2.f;
+  const float fx = (1.f + w * t0) + (y * t2 - z * t1);
+  const float fy = (0.f + w * t1) + (z * t0 - x * t2);
+  const float two_pi = 6.2831855f, pi = 3.1415927f;
+  float a = fmodf(atan2f(fy, fx), two_pi);
+  if (a != 0.f && a < 0.f) a += two_pi;
+  if (a > pi) a -= two_pi;
+  return fminf(fmaxf(0.5f * a, -1.f), 1.f);
+}
+// V: the root's world linear velocity as root_states reports it after the step (after _push_robots)
 __device__ __forceinline__ void obs_base_values(const lrl_env_params& P, V3 blv, V3 bav, V3 pg, const float* cmd,
-                                                float* ob) {
+                                                const float* quat, const float* V, float* ob) {
   int o = 0;
-  if (P.observe_vel) {
+  if (P.observe_only_lin_vel) {
     ob[o++] = blv.x * P.obs_scale_lin_vel; ob[o++] = blv.y * P.obs_scale_lin_vel; ob[o++] = blv.z * P.obs_scale_lin_vel;
+  }
+  if (P.observe_only_ang_vel) {
+    ob[o++] = bav.x * P.obs_scale_ang_vel; ob[o++] = bav.y * P.obs_scale_ang_vel; ob[o++] = bav.z * P.obs_scale_ang_vel;
+  }
+  if (P.observe_vel) {
+    if (P.global_reference) {  // (:361-364: the world velocity; the angular block stays base frame)
+      ob[o++] = V[0] * P.obs_scale_lin_vel; ob[o++] = V[1] * P.obs_scale_lin_vel; ob[o++] = V[2] * P.obs_scale_lin_vel;
+    } else {
+      ob[o++] = blv.x * P.obs_scale_lin_vel; ob[o++] = blv.y * P.obs_scale_lin_vel; ob[o++] = blv.z * P.obs_scale_lin_vel;
+    }
     ob[o++] = bav.x * P.obs_scale_ang_vel; ob[o++] = bav.y * P.obs_scale_ang_vel; ob[o++] = bav.z * P.obs_scale_ang_vel;
   }
   ob[o++] = pg.x; ob[o++] = pg.y; ob[o++] = pg.z;
@@ -2185,6 +2217,7 @@ __device__ __forceinline__ void obs_base_values(const lrl_env_params& P, V3 blv,
 #pragma unroll
     for (int k = 0; k < 3; ++k) ob[o++] = cmd[k] * P.commands_scale[k];
   }
+  if (P.observe_yaw) ob[o + 36] = obs_yaw_value(quat);  // after the 36 joint entries, before the height rows
 }
 __device__ __forceinline__ void obs_noise_clip(const lrl_env_params& P, const KState& S, int e, uint64_t genv,
                                                int64_t step_counter, bool inject, float* ob, int c0, int cstep) {
@@ -2513,6 +2546,10 @@ __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restri
     st.V[0] = P.push_span * u0 + P.push_lo;  // (upper - lower) * torch.rand + lower
     st.V[1] = P.push_span * u1 + P.push_lo;
   }
+  // global_reference's tracking_lin_vel error (:1580-1581: against root_states[:, 7:9], the world velocity after the
+  // push), taken here where the velocity is in registers: one value carried to the reward loop instead of two
+  float gerr = 0.f;
+  if (P.global_reference) gerr = sq(cmd[0] - st.V[0]) + sq(cmd[1] - st.V[1]);
   // termination (legged_robot.py:190-202): the contact test above, the body height, and (upstream) the time-out
   if (P.use_terminal_body_height && st.pos[2] < P.terminal_body_height) rst = 1;
   // time-outs (legged_robot.py:196-198, commented out in the fork — Q2): upstream semantics only
@@ -2568,7 +2605,7 @@ __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restri
   // entries; the same expressions, so the same values as one lane writing the row
   {
     float* ob = otile + es * NO;
-    const int o = (P.observe_vel ? 6 : 0) + 3 + (P.observe_command ? 3 : 0);
+    const int o = obs_joint_offset(P);
     const int qi = mirror_quad();  // (one quad per env on the terrain mesh: it writes all four groups)
     if (MIRROR == 1 || qi == 0) {
 #pragma unroll
@@ -2582,7 +2619,7 @@ __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restri
 #pragma unroll
       for (int j = 0; j < 3; ++j) ob[o + 24 + 3 * ql + j] = act3[j];
     }
-    if ((MIRROR == 1 || qi == 3) && ql == 0) obs_base_values(P, blv, bav, pg, cmd, ob);
+    if ((MIRROR == 1 || qi == 3) && ql == 0) obs_base_values(P, blv, bav, pg, cmd, quat, st.V, ob);
   }
   // post-physics rewards, observations and the per-env state write-back: lane 0 of each env (of its first quad)
   if (ql == 0 && mirror_quad() == 0) {
@@ -2650,6 +2687,7 @@ __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restri
       case LRL_R_TORQUE_LIMITS: r = jt[8]; break;
       case LRL_R_TRACKING_LIN_VEL: {
         float err = sq(cmd[0] - blv.x) + sq(cmd[1] - blv.y);
+        if (P.global_reference) err = gerr;
         r = expf(-err / P.tracking_sigma);
       } break;
       case LRL_R_TRACKING_ANG_VEL: r = expf(-sq(cmd[2] - bav.z) / P.tracking_sigma_yaw); break;
@@ -2896,16 +2934,26 @@ inline namespace LRL_ENV_NS {
 // Every element's value, draw and operation order are the step kernel's (obs_base_values + its quads' joint entries /
 // obs_noise_clip), so the rows are bit-identical.
 constexpr int OBS_LANES = 16;
-// observation entry i of env e (the step kernel's layout: [lin vel, ang vel,] gravity, [commands,] dof pos, dof vel,
-// actions, then the height rows against base height z)
+// observation entry i of env e (the step kernel's layout: [only lin vel,] [only ang vel,] [lin vel, ang vel,] gravity,
+// [commands,] dof pos, dof vel, actions, [yaw,] then the height rows against base height z)
 __device__ __forceinline__ float obs_entry(const lrl_env_params& P, const KState& S, int e, int i, V3 blv, V3 bav,
                                            V3 pg) {
   const int N = S.stride;
   int o = 0;
-  if (P.observe_vel) {
+  if (P.observe_only_lin_vel) {
     if (i < 3) return (i == 0 ? blv.x : i == 1 ? blv.y : blv.z) * P.obs_scale_lin_vel;
-    if (i < 6) return (i == 3 ? bav.x : i == 4 ? bav.y : bav.z) * P.obs_scale_ang_vel;
-    o = 6;
+    o = 3;
+  }
+  if (P.observe_only_ang_vel) {
+    if (i < o + 3) return (i == o ? bav.x : i == o + 1 ? bav.y : bav.z) * P.obs_scale_ang_vel;
+    o += 3;
+  }
+  if (P.observe_vel) {
+    if (i < o + 3)
+      return (P.global_reference ? S.root[(7 + i - o) * N + e] : (i == o ? blv.x : i == o + 1 ? blv.y : blv.z)) *
+             P.obs_scale_lin_vel;
+    if (i < o + 6) return (i == o + 3 ? bav.x : i == o + 4 ? bav.y : bav.z) * P.obs_scale_ang_vel;
+    o += 6;
   }
   if (i < o + 3) return i == o ? pg.x : i == o + 1 ? pg.y : pg.z;
   o += 3;
@@ -2916,6 +2964,12 @@ __device__ __forceinline__ float obs_entry(const lrl_env_params& P, const KState
   if (i < o + 12) return (S.dof_pos[(i - o) * N + e] - P.default_dof_pos[i - o]) * P.obs_scale_dof_pos;
   if (i < o + 24) return S.dof_vel[(i - o - 12) * N + e] * P.obs_scale_dof_vel;
   if (i < o + 36) return S.actions[(i - o - 24) * N + e];
+  if (P.observe_yaw && i == o + 36) {
+    float q[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = S.root[(3 + k) * N + e];
+    return obs_yaw_value(q);
+  }
   const int k = i - (P.num_obs - P.num_height_points);  // height row k (measure_heights)
   return fminf(fmaxf(S.root[2 * N + e] - 0.5f - S.heights[k * N + e], -1.f), 1.f) * P.obs_scale_height;
 }

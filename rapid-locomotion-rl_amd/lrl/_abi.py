@@ -76,6 +76,7 @@ class LrlEnvParams(C.Structure):
         ("joint_limits", i32), ("joint_limit_margin", f32), ("self_collisions", i32),
         ("push_robots", i32), ("push_interval", i32), ("push_lo", f32), ("push_span", f32),
         ("solver_tgs", i32),
+        ("observe_only_ang_vel", i32), ("observe_only_lin_vel", i32), ("observe_yaw", i32), ("global_reference", i32),
     ]
 
 

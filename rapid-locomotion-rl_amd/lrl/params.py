@@ -53,15 +53,23 @@ def reward_layout(cfg):
 
 
 def noise_vec(cfg):
-    """legged_robot.py:882-932 (only the layouts the kernel implements)."""
+    """legged_robot.py:882-932, one entry per observation.  The reference adds nothing for observe_only_ang_vel
+    (its vector is then 3 short of the row, and ``obs_buf += ... * noise_scale_vec`` raises with add_noise:
+    build_params refuses that case the same way); those 3 entries are zero here and never used."""
     ns, lvl, s = cfg.noise.noise_scales, cfg.noise.noise_level, cfg.normalization.obs_scales
     parts = []
+    if cfg.env.observe_only_lin_vel:  # :914-917
+        parts += [ns.lin_vel * lvl * s.lin_vel] * 3
+    if cfg.env.observe_only_ang_vel:
+        parts += [0.0] * 3
     if cfg.env.observe_vel:
         parts += [ns.lin_vel * lvl * s.lin_vel] * 3 + [ns.ang_vel * lvl * s.ang_vel] * 3
     parts += [ns.gravity * lvl] * 3
     if cfg.env.observe_command:
         parts += [0.0] * 3
     parts += [ns.dof_pos * lvl * s.dof_pos] * 12 + [ns.dof_vel * lvl * s.dof_vel] * 12 + [0.0] * 12
+    if cfg.env.observe_yaw:  # :919-922
+        parts += [0.0]
     if cfg.terrain.measure_heights:  # :924-927
         parts += [ns.height_measurements * lvl * s.height_measurements] * len(height_points(cfg))
     return np.array(parts, np.float32)
@@ -154,9 +162,9 @@ def build_params(cfg, robot, auto_reset=False, solver_iterations=None, baumgarte
     n_obs = cfg.env.num_observations
     if len(nv) != n_obs:
         raise ValueError(f"observation layout has {len(nv)} entries but num_observations={n_obs}")
-    for flag in ("observe_only_ang_vel", "observe_only_lin_vel", "observe_yaw"):
-        if getattr(cfg.env, flag):
-            raise ValueError(f"Cfg.env.{flag} is not implemented by the fused kernel")
+    if cfg.env.observe_only_ang_vel and cfg.noise.add_noise:  # :392 with the 3-short vector of :882-932
+        raise RuntimeError(f"The size of tensor a ({n_obs}) must match the size of tensor b ({n_obs - 3}) at "
+                           "non-singleton dimension 1")
     mt = cfg.terrain.mesh_type
     if cfg.terrain.measure_heights and mt == "none":
         raise NameError("Can't measure height with terrain mesh type 'none'")  # :1484-1485
@@ -229,5 +237,8 @@ def build_params(cfg, robot, auto_reset=False, solver_iterations=None, baumgarte
         push_robots=int(bool(dr0.push_robots)), push_interval=int(cfg.domain_rand.push_interval),
         push_lo=-push_max, push_span=push_max - (-push_max),
         solver_tgs=int((physx.solver_type if solver_type is None else solver_type) == 1 and not terrain_mesh),
+        observe_only_ang_vel=int(bool(cfg.env.observe_only_ang_vel)),
+        observe_only_lin_vel=int(bool(cfg.env.observe_only_lin_vel)), observe_yaw=int(bool(cfg.env.observe_yaw)),
+        global_reference=int(bool(cfg.commands.global_reference)),
     )
     return P
