@@ -339,7 +339,6 @@ __global__ __launch_bounds__(CD_THREADS) void curriculum_dev_kernel(CurDevArgs a
       __syncthreads();
       if (t == 0) Ssum = 0.0 + cd_walk(nb, 1, nullptr, nullptr, leaf_val, nullptr, cstack);
     }
-    if (t == 0 && a.log_area) c.command_area[0] = Ssum / (double)nb;
     __syncthreads();
   }
   // ---- the sampling cdf (cached while the weights are unchanged), staged in LDS ----
@@ -399,6 +398,8 @@ __global__ __launch_bounds__(CD_THREADS) void curriculum_dev_kernel(CurDevArgs a
   } else {
     for (int b = t; b < nb; b += CD_THREADS) cdf[b] = c.cdf[b];
   }
+  // (after choice's checks: the host's reset_idx never reaches its area log when the sample raises)
+  if (t == 0 && a.log_area) c.command_area[0] = Ssum / (double)nb;
   __syncthreads();
   // ---- the draws: n choice doubles, then 3 n uniform doubles (2 words each) ----
   for (int i = t; i < MT_N; i += CD_THREADS) key[i] = c.mt_key[i];

@@ -1,4 +1,6 @@
 """Shared test helpers: configs, fixture loading, oracle state set-up."""
+import contextlib
+import functools
 import json
 import os
 
@@ -249,3 +251,94 @@ def record_errors(tag, got, st, excluded, alt=None):
         i = sum(1 for _ in open(path)) - 1
         np.savez_compressed(path.replace(".jsonl", f"_{i:03d}.npz"), tag=np.array(tag), **arrs)
     return rec
+
+
+# ---- sims made through the C ABI (lrl_sim_create) and device buffers for the kernel tests; torch is imported on use,
+# so that the CPU tests that share this module do not need it ----
+DEV = "cuda:0"
+
+
+def vp(t):
+    import ctypes as C
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def dev(a, dtype=None):
+    import torch
+    return torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32 if dtype is None else dtype, device=DEV)
+
+
+def npy(t):
+    return t.detach().cpu().numpy()
+
+
+def stream():
+    from lrl import _abi
+    return _abi.stream_of(DEV)
+
+
+def sync():
+    import torch
+    torch.cuda.synchronize()
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+def same(got, want, what=""):
+    """Bit-for-bit equality (NaN payloads and signed zeros included)."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
+    bad = bits(got) != bits(want)
+    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} differ, first at {np.argwhere(bad)[0]}"
+
+
+class Sim:
+    """An lrl_sim and torch views of its tensors."""
+
+    def __init__(self, M, P, n, offset=0, seed=1):
+        import ctypes as C
+
+        import torch
+        from lrl import _abi
+        self.L = _abi.lib()
+        self.h = C.c_void_p()
+        self.n, self.M, self.P = n, M, P
+        torch.cuda.set_device(0)
+        _abi.check(self.L.lrl_sim_create(C.byref(M), C.byref(P), C.c_int32(n), C.c_int64(offset), C.c_uint64(seed),
+                                         C.c_int32(0), C.byref(self.h)))
+        self._views = {}
+
+    def t(self, tid):
+        import ctypes as C
+        from lrl import _abi, _dlpack
+        if tid not in self._views:
+            d = _abi.LrlTensor()
+            _abi.check(self.L.lrl_sim_tensor(self.h, C.c_int32(tid), C.byref(d)))
+            self._views[tid] = _dlpack.wrap(d, 0)
+        return self._views[tid]
+
+    def close(self):
+        sync()
+        self.L.lrl_sim_destroy(self.h)
+
+
+@contextlib.contextmanager
+def sim_of(M, P, n, offset=0, seed=1):
+    s = Sim(M, P, n, offset, seed)
+    try:
+        yield s
+    finally:
+        s.close()
+
+
+@functools.lru_cache(None)
+def _mc():
+    return make("mc")
+
+
+def mc_sim(n, offset=0, seed=1):
+    _, _, M, P = _mc()
+    return sim_of(M, P, n, offset, seed)

@@ -24,7 +24,6 @@ Everything else is exact: id lists, step codes, history shifts, setters and the 
 bit (the RNG against the Philox restatement that test_aux_ref.py pins on the Random123 known answers), the episode
 means within the rounding bound of their reduction.  No test passes an env id outside [0, n).
 """
-import contextlib
 import ctypes as C
 import functools
 
@@ -33,90 +32,13 @@ import pytest
 import torch
 
 import aux_ref as ar
-from helpers import make, make_rough
-from lrl import _abi, _dlpack
+from helpers import DEV, dev, make, make_rough, mc_sim, npy, same, sim_of, stream, sync, vp
+from lrl import _abi
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 F32 = np.float32
 i32, i64, f32c, u32c = C.c_int32, C.c_int64, C.c_float, C.c_uint32
-
-
-def vp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def dev(a, dtype=torch.float32):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device=DEV)
-
-
-def npy(t):
-    return t.detach().cpu().numpy()
-
-
-def stream():
-    return _abi.stream_of(DEV)
-
-
-def sync():
-    torch.cuda.synchronize()
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def same(got, want, what=""):
-    """Bit-for-bit equality (NaN payloads and signed zeros included)."""
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    bad = bits(got) != bits(want)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} differ, first at {np.argwhere(bad)[0]}"
-
-
-class Sim:
-    """An lrl_sim and torch views of its tensors."""
-
-    def __init__(self, M, P, n, offset=0, seed=1):
-        self.L = _abi.lib()
-        self.h = C.c_void_p()
-        self.n, self.M, self.P = n, M, P
-        torch.cuda.set_device(0)
-        _abi.check(self.L.lrl_sim_create(C.byref(M), C.byref(P), i32(n), i64(offset), C.c_uint64(seed), i32(0),
-                                         C.byref(self.h)))
-        self._views = {}
-
-    def t(self, tid):
-        if tid not in self._views:
-            d = _abi.LrlTensor()
-            _abi.check(self.L.lrl_sim_tensor(self.h, i32(tid), C.byref(d)))
-            self._views[tid] = _dlpack.wrap(d, 0)
-        return self._views[tid]
-
-    def close(self):
-        sync()
-        self.L.lrl_sim_destroy(self.h)
-
-
-@contextlib.contextmanager
-def sim_of(M, P, n, offset=0, seed=1):
-    s = Sim(M, P, n, offset, seed)
-    try:
-        yield s
-    finally:
-        s.close()
-
-
-@functools.lru_cache(None)
-def _mc():
-    return make("mc")
-
-
-def mc_sim(n, offset=0, seed=1):
-    _, _, M, P = _mc()
-    return sim_of(M, P, n, offset, seed)
 
 
 @functools.lru_cache(None)
