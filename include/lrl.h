@@ -669,8 +669,9 @@ int32_t lrl_debug_sim_arena(lrl_sim* s, void** arena, int64_t* bytes, int64_t* s
 /* Test entry point of the GEMM the update is built from: C = op(A) op(B) with
  * layout 0 (NT: C[m][n] = sum_k A[m][k] B[n][k]), 2 (NN: sum_k A[m][k] B[k][n]),
  * 3 (TN: sum_k A[k][m] B[k][n], split over k, partials reduced in place);
- * epi 0 store, 1 +bias[n], 2 elu(+bias[n]), 3 *elu'(aux[m][n]), 5 tanh(+bias[n]) (NT only), 6 *(1 - aux[m][n]^2)
- * (NN only; aux = the tanh output of the layer input).  rows (optional) gathers A's rows
+ * epi 0 store, 1 +bias[n], 2 elu(+bias[n]), 3 *elu'(aux[m][n]), 5 tanh(+bias[n]), 6 *(1 - aux[m][n]^2) (aux = the
+ * activation output of the layer input).  The pairs on offer are NT with epi 0, 1, 2, 5, NN with epi 0, 3, 6 and TN
+ * (always the split product); any other pair is refused, whatever the shape.  rows (optional) gathers A's rows
  * (NT/NN) or B's rows (TN).  layout | 0x100 (NT / NN): B is first split into hi / mid / lo bf16 planes in the
  * workspace (3 * N * round16(K) / 2 floats) and the product runs on the pre-split-B kernel the update uses for its
  * weight products, or fails if the shape is not one it takes. */

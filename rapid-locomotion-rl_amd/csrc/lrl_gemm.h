@@ -10,12 +10,15 @@
 // RolloutStorage.mini_batch_generator (rollout_storage.py:100-137) — so the minibatch is never copied.
 //
 // The fp32 MFMA kernels behind the launcher (gemm_launch picks by shape; the bf16-split families it tries first —
-// x6, x6d, x6p, x6t — are described in lrl_gemm.hip, the dispatch table is DESIGN.md §3):
+// x6, x6d, x6p, x6t — are described in lrl_gemm.hip, the dispatch table is DESIGN.md §3).  The (layout, epilogue)
+// pairs on offer are NT with EPI_STORE / BIAS / BIAS_ELU / BIAS_TANH, NN with EPI_STORE / DELU / DTANH (and
+// EPI_PARTIAL, register-staged only) and TN with EPI_PARTIAL; gemm_launch refuses any other pair before a family is
+// tried, and no family instantiates one:
 //  * LDS-DMA (NT / NN, every tile interior, float4-aligned operands): 64 x 64 tile, 16-k slices land in a
 //    3-stage LDS ring straight from global memory (global_load_lds_dwordx4, counted vmcnt waits, swizzled
 //    images read with ds_read_b128), two accumulators per wave;
-//  * thin (NT / NN, N <= 32, k = 512 / 1024): op(B) kept in registers per k-quarter, A streamed a block
-//    ahead, quarter sums added in wave order;
+//  * thin (NT, and NN with EPI_STORE; N <= 32, k = 512 / 1024): op(B) kept in registers per k-quarter, A streamed a
+//    block ahead, quarter sums added in wave order;
 //  * register-staged (everything else, incl. the split-k weight gradients): a workgroup (4 waves) owns a
 //    BM x BN tile (128 / 64 wide, 32 for thin layers); 16-k slices stage through LDS k-major so each MFMA
 //    operand is one ds_read_b32 per lane; the next slice is prefetched into registers while the current one
@@ -38,8 +41,8 @@ enum GemmEpi : int {
   EPI_BIAS_ELU = 2,  // C = elu(acc + bias[n])
   EPI_DELU = 3,      // C = acc * elu'(aux[m][n])  (aux = ELU output of the layer input: elu' = aux > 0 ? 1 : aux + 1)
   EPI_PARTIAL = 4,   // split-k partial: C + split * part_stride (+ bias-gradient partial of A's columns)
-  EPI_BIAS_TANH = 5, // C = tanh(acc + bias[n])  (NT products only)
-  EPI_DTANH = 6,     // C = acc * (1 - aux[m][n]^2)  (NN products only; aux = tanh output of the layer input)
+  EPI_BIAS_TANH = 5, // C = tanh(acc + bias[n])
+  EPI_DTANH = 6,     // C = acc * (1 - aux[m][n]^2)  (aux = tanh output of the layer input)
 };
 
 struct GemmP {

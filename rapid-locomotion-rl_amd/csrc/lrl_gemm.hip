@@ -28,6 +28,12 @@ constexpr int GTHREADS = 256;
 // instead of the 16-row one
 static int g_path_off = 0;
 static int path_off() { return __atomic_load_n(&g_path_off, __ATOMIC_RELAXED); }
+// a path switch from the environment: the variable's first character when that is a digit, dflt otherwise (callers
+// read it once, into a function-local static)
+static int env_switch(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e && e[0] >= '0' && e[0] <= '9' ? e[0] - '0' : dflt;
+}
 
 // family / tile of this thread's last launch (gemm_last_path): one thread-local store per launch
 static thread_local int g_last_path = 0;
@@ -77,6 +83,51 @@ __device__ __forceinline__ float tanh_f(float x) { return tanhf(x); }
 // epilogue classes: a bias vector added before the activation / the layer input's activation output read as aux
 __host__ __device__ constexpr bool epi_bias(int e) { return e == EPI_BIAS || e == EPI_BIAS_ELU || e == EPI_BIAS_TANH; }
 __host__ __device__ constexpr bool epi_aux(int e) { return e == EPI_DELU || e == EPI_DTANH; }
+// the epilogue's value: v = the accumulator, bj = the column's bias, x = the aux operand (kernels of families without
+// an aux epilogue pass 0)
+template <int EPI>
+__device__ __forceinline__ float epi_apply(float v, float bj, float x) {
+  if constexpr (EPI == EPI_BIAS) return v + bj;
+  else if constexpr (EPI == EPI_BIAS_ELU) return elu_f(v + bj);
+  else if constexpr (EPI == EPI_BIAS_TANH) return tanh_f(v + bj);
+  else if constexpr (EPI == EPI_DELU) return x > 0.f ? v : v * (x + 1.f);
+  else if constexpr (EPI == EPI_DTANH) return v * (1.f - x * x);
+  else return v;
+}
+
+// ---- dispatch: a runtime (layout, epilogue) pair to a template instantiation ----
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <int... V>
+struct Ints {};
+// f(Int<V>{}) for the V of the list that equals v; LRL_E_INVALID when none does (there is no default instantiation)
+template <int... V, class F>
+static int with_int(int v, Ints<V...>, F&& f) {
+  int rc = LRL_E_INVALID;
+  (void)((v == V && ((rc = f(Int<V>{})), true)) || ...);
+  return rc;
+}
+// The pairs the library offers, stated once.  STAGED: the register-staged family, which alone also takes a split
+// backward-data product (NN + EPI_PARTIAL).
+template <int LAYOUT, bool STAGED>
+struct Offered;
+template <bool STAGED>
+struct Offered<GEMM_NT, STAGED> { using epis = Ints<EPI_STORE, EPI_BIAS, EPI_BIAS_ELU, EPI_BIAS_TANH>; };
+template <>
+struct Offered<GEMM_NN, false> { using epis = Ints<EPI_STORE, EPI_DELU, EPI_DTANH>; };
+template <>
+struct Offered<GEMM_NN, true> { using epis = Ints<EPI_STORE, EPI_DELU, EPI_DTANH, EPI_PARTIAL>; };
+template <bool STAGED>
+struct Offered<GEMM_TN, STAGED> { using epis = Ints<EPI_PARTIAL>; };
+using BatchMajor = Ints<GEMM_NT, GEMM_NN>;
+using AnyLayout = Ints<GEMM_NT, GEMM_NN, GEMM_TN>;
+// f(Int<layout>{}, Int<epi>{}) when layout is one of the family's LAYOUTS and the pair is offered, else LRL_E_INVALID
+template <bool STAGED = false, int... LAYOUTS, class F>
+static int with_pair(int layout, int epi, Ints<LAYOUTS...> layouts, F&& f) {
+  return with_int(layout, layouts, [&](auto L) {
+    return with_int(epi, typename Offered<decltype(L)::value, STAGED>::epis{}, [&](auto E) { return f(L, E); });
+  });
+}
 
 // load 4 consecutive floats (all in range) with the widest access the operand's alignment allows
 __device__ __forceinline__ float4 load4(const float* __restrict__ src, int vec) {
@@ -341,15 +392,8 @@ __global__ __launch_bounds__(GTHREADS) void gemm_kernel(GemmP p) {
       for (int r = 0; r < 16; ++r) {
         const int row = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
         if (row < p.M) {
-          float v = NACC == 2 ? acc[i][j][r] + acc2[i][j][r] : acc[i][j][r];
-          if (EPI == EPI_BIAS) v += bj;
-          if (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
-          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
-          if constexpr (epi_aux(EPI)) {
-            const float x = xaux[i][j][r];
-            v = EPI == EPI_DTANH ? v * (1.f - x * x) : (x > 0.f ? v : v * (x + 1.f));
-          }
-          C[(int64_t)row * p.ldc + col] = v;
+          const float v = NACC == 2 ? acc[i][j][r] + acc2[i][j][r] : acc[i][j][r];
+          C[(int64_t)row * p.ldc + col] = epi_apply<EPI>(v, bj, epi_aux(EPI) ? xaux[i][j][r] : 0.f);
         }
       }
     }
@@ -361,21 +405,29 @@ __global__ __launch_bounds__(GTHREADS) void gemm_kernel(GemmP p) {
 
 // ---------------------------------------------------------------------------------------------------
 // LDS-DMA variant for the interior batch-major products (forward NT, backward-data NN) with float4-aligned
-// operands: 64x64 tile, 4 waves each owning a 32x32 MFMA tile, BK = 16, a 3-deep ring of LDS stages
-// filled by global_load_lds_dwordx4 (no staging registers, no ds_write pass), counted vmcnt waits and a
-// raw s_barrier so the loads of slice k+2 stay in flight while slice k is consumed.
-//   k-contiguous operands (A; B of NT) land as [row][16 k] images, 16-B chunk c of row r stored in slot
-//   c ^ ((r >> 2) & 3) (the swizzle is applied to the SOURCE address, the DMA destination stays lane-linear),
-//   and each lane reads its row's 8 k-values (k = 8h .. 8h+7) with two conflict-free ds_read_b128;
-//   the n-contiguous B of NN lands as [16 k][64 n] and is read with ds_read_b32 (consecutive n per lane).
-// MFMA k-step t of lane half h uses k = 8h + t for both operands, so the sum runs over every k once.
+// operands ("glds", BKD = 16; "glds32", BKD = 32, for k a multiple of 32): 64x64 tile, 4 waves each owning a 32x32
+// MFMA tile, a 3-deep ring of BKD-k LDS stages filled by global_load_lds_dwordx4 (no staging registers, no ds_write
+// pass), counted vmcnt waits and a raw s_barrier so the loads of slice k+2 stay in flight while slice k is consumed;
+// 8 (BKD = 16) or 16 MFMAs per wave between barriers.
+//   k-contiguous operands (A; B of NT) land as [row][BKD k] images, 16-B chunk c of row r stored in slot
+//   c ^ ((r >> 2) & 3) (BKD = 16: 64-B rows) or c ^ ((r >> 1) & 7) (BKD = 32: 128-B rows, so the 8 lanes of a
+//   ds_read_b128 group, 8 consecutive rows of one chunk, hit 8 distinct 16-B bank groups); the swizzle is applied to
+//   the SOURCE address, the DMA destination stays lane-linear: DMA d of a slice fills rows 16d .. 16d+15 (lane l: row
+//   16d + l / 4, slot l % 4) or 8d .. 8d+7 (row 8d + l / 8, slot l % 8), one or two DMAs per wave and operand.  Each
+//   lane reads its row's BKD / 2 k-values (k = BKD / 2 h ..) with conflict-free ds_read_b128;
+//   the n-contiguous B of NN lands as [BKD k][64 n] (DMA d filling k-rows 4d .. 4d+3) and is read with ds_read_b32
+//   (consecutive n per lane).
+// MFMA k-step t of lane half h uses k = BKD / 2 h + t for both operands, so the sum runs over every k once.
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-template <int LAYOUT, int EPI>
+template <int LAYOUT, int EPI, int BKD>
 __global__ __launch_bounds__(GTHREADS) void gemm_glds_kernel(GemmP p) {
-  constexpr int BM = 64, BN = 64, BKD = 16, NST = 3, IMG = 1024;
+  constexpr int BM = 64, BN = 64, NST = 3, IMG = 64 * BKD;
+  constexpr int CPR = BKD / 4, NDMA = BKD / 16;  // 16-B chunks per image row; DMAs per wave, operand and slice
+  constexpr int SWS = BKD == 16 ? 2 : 1;         // chunk c of row r sits in slot c ^ ((r >> SWS) & (CPR - 1))
   constexpr bool BNC = (LAYOUT & 2) != 0;
   static_assert((LAYOUT & 1) == 0, "A must be k-contiguous");
+  static_assert(BKD == 16 || BKD == 32, "image layouts");
   __shared__ __attribute__((aligned(16))) float S[NST * 2 * IMG];  // [stage][A | B][image], one LDS object
   const int mt = p.M / BM, nt = p.N / BN;
   int L;
@@ -392,16 +444,17 @@ __global__ __launch_bounds__(GTHREADS) void gemm_glds_kernel(GemmP p) {
   const int li = lane & 31, h = lane >> 5;
   const int wm = (w >> 1) * 32, wn = (w & 1) * 32;
   const int K = p.K;
-
-  // this lane's DMA sources: A rows 16w + lane/4 (chunk pre-swizzled); B likewise (NT) or k-row 4w + lane/16 (NN)
-  const int ar = 16 * w + (lane >> 2);
-  const int achunk = (lane & 3) ^ ((ar >> 2) & 3);
-  const float* asrc = A + (p.a_rows ? p.a_rows[m0 + ar] : (int64_t)(m0 + ar)) * p.lda + 4 * achunk;
-  const float* bsrc;
-  if constexpr (!BNC) {
-    bsrc = B + (int64_t)(n0 + ar) * p.ldb + 4 * achunk;
-  } else {
-    bsrc = B + (int64_t)(4 * w + (lane >> 4)) * p.ldb + n0 + 4 * (lane & 15);
+  // this lane's DMA sources: DMA d = NDMA w + i fills A rows (64 / CPR) d + lane / CPR (chunk pre-swizzled); B likewise
+  // (NT) or k-rows 4d + lane / 16 (NN)
+  const float* asrc[NDMA];
+  const float* bsrc[NDMA];
+#pragma unroll
+  for (int i = 0; i < NDMA; ++i) {
+    const int d = NDMA * w + i, row = (64 / CPR) * d + lane / CPR;
+    const int chunk = (lane % CPR) ^ ((row >> SWS) & (CPR - 1));
+    asrc[i] = A + (p.a_rows ? p.a_rows[m0 + row] : (int64_t)(m0 + row)) * p.lda + 4 * chunk;
+    if constexpr (!BNC) bsrc[i] = B + (int64_t)(n0 + row) * p.ldb + 4 * chunk;
+    else bsrc[i] = B + (int64_t)(4 * d + (lane >> 4)) * p.ldb + n0 + 4 * (lane & 15);
   }
   // the DMA is issued from inline asm so the compiler does not track it (it would otherwise drain it with
   // vmcnt(0) before every ds_read); completion is ordered by the counted waits below
@@ -414,11 +467,14 @@ __global__ __launch_bounds__(GTHREADS) void gemm_glds_kernel(GemmP p) {
                  : "memory");
   };
   auto issue = [&](int st, int k0) {
-    const uint32_t base = __builtin_amdgcn_readfirstlane(s_lds + (uint32_t)((st * 2 * IMG + w * 256) * 4));
-    dma(asrc + k0, base);
-    dma(BNC ? bsrc + (int64_t)k0 * p.ldb : bsrc + k0, base + IMG * 4);
+#pragma unroll
+    for (int i = 0; i < NDMA; ++i) {
+      const uint32_t base =
+          __builtin_amdgcn_readfirstlane(s_lds + (uint32_t)((st * 2 * IMG + (NDMA * w + i) * 256) * 4));
+      dma(asrc[i] + k0, base);
+      dma(BNC ? bsrc[i] + (int64_t)k0 * p.ldb : bsrc[i] + k0, base + IMG * 4);
+    }
   };
-
   // backward-data epilogue operand (elu' of the layer input), fetched before the DMA ring starts
   float xaux[16];
   if constexpr (epi_aux(EPI)) {
@@ -430,156 +486,46 @@ __global__ __launch_bounds__(GTHREADS) void gemm_glds_kernel(GemmP p) {
       xaux[r] = ax[(int64_t)row * p.ld_aux + col];
     }
   }
-
   f32x16 acc, acc2;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = acc2[r] = 0.f;
-
   const int ns = K / BKD;
   issue(0, 0);
   if (ns > 1) issue(1, BKD);
-  const int ai = wm + li, aswz = (ai >> 2) & 3;
-  const int bi = wn + li, bswz = (bi >> 2) & 3;
+  const int ai = wm + li, aswz = (ai >> SWS) & (CPR - 1);
+  const int bi = wn + li, bswz = (bi >> SWS) & (CPR - 1);
   for (int s = 0; s < ns; ++s) {
-    // this wave's DMA of slice s has landed (slice s+1's two loads may stay in flight) ...
-    if (s + 1 < ns) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // this wave's DMA of slice s has landed (slice s+1's 2 NDMA loads may stay in flight) ...
+    if (s + 1 < ns) {
+      if constexpr (NDMA == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     // ... and every wave's, and every wave is done reading the stage slice s+2 will overwrite
     __builtin_amdgcn_s_barrier();
     if (s + 2 < ns) issue((s + 2) % NST, (s + 2) * BKD);
     const float* As = S + (s % NST) * 2 * IMG;
     const float* Bs = As + IMG;
-    float a[8], b[8];
-    {
+    float a[BKD / 2], b[BKD / 2];
+    // a row's BKD / 2 k-values of lane half h: its chunks BKD / 8 * h + q.  (The two chunks of BKD = 16 are spelled out:
+    // as a loop they compile to another address computation than this kernel had while it was a kernel of its own.)
+    if constexpr (BKD == 16) {
       const float4 a0 = *reinterpret_cast<const float4*>(As + ai * 16 + 4 * ((2 * h) ^ aswz));
       const float4 a1 = *reinterpret_cast<const float4*>(As + ai * 16 + 4 * ((2 * h + 1) ^ aswz));
       a[0] = a0.x; a[1] = a0.y; a[2] = a0.z; a[3] = a0.w; a[4] = a1.x; a[5] = a1.y; a[6] = a1.z; a[7] = a1.w;
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 v = *reinterpret_cast<const float4*>(As + ai * 32 + 4 * ((4 * h + q) ^ aswz));
+        a[4 * q] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
+      }
     }
-    if constexpr (!BNC) {
+    if constexpr (!BNC && BKD == 16) {
       const float4 b0 = *reinterpret_cast<const float4*>(Bs + bi * 16 + 4 * ((2 * h) ^ bswz));
       const float4 b1 = *reinterpret_cast<const float4*>(Bs + bi * 16 + 4 * ((2 * h + 1) ^ bswz));
       b[0] = b0.x; b[1] = b0.y; b[2] = b0.z; b[3] = b0.w; b[4] = b1.x; b[5] = b1.y; b[6] = b1.z; b[7] = b1.w;
-    } else {
-#pragma unroll
-      for (int t = 0; t < 8; ++t) b[t] = Bs[(8 * h + t) * BN + bi];
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      if (t & 1) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b[t], acc2, 0, 0, 0);
-      else acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b[t], acc, 0, 0, 0);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-
-  float* __restrict__ C = p.C + g * p.gc;
-  const int col = n0 + wn + li;
-  float bj = 0.f;
-  if constexpr (epi_bias(EPI)) bj = p.bias[g * p.gbias + col];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * h;
-    float v = acc[r] + acc2[r];
-    if constexpr (EPI == EPI_BIAS) v += bj;
-    if constexpr (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
-          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
-    if constexpr (epi_aux(EPI)) {
-      const float x = xaux[r];
-      v = EPI == EPI_DTANH ? v * (1.f - x * x) : (x > 0.f ? v : v * (x + 1.f));
-    }
-    C[(int64_t)row * p.ldc + col] = v;
-  }
-}
-
-
-// BK = 32 variant of the LDS-DMA kernel (k a multiple of 32): 16 MFMAs per wave between barriers instead
-// of 8.  [row][32 k] images (128-B rows): 16-B chunk c of row r sits in slot c ^ ((r >> 1) & 7), so the 8
-// lanes of a ds_read_b128 group (8 consecutive rows, one chunk) hit 8 distinct 16-B bank groups; DMA d of a
-// slice fills rows 8d .. 8d+7 (lane l: row 8d + l / 8, slot l % 8, source chunk pre-swizzled).  The NN B image
-// is [32 k][64 n], DMA d filling k-rows 4d .. 4d+3.  Lane half h uses k = 16h .. 16h+15 at MFMA steps 0..15.
-template <int LAYOUT, int EPI>
-__global__ __launch_bounds__(GTHREADS) void gemm_glds32_kernel(GemmP p) {
-  constexpr int BM = 64, BN = 64, BKD = 32, NST = 3, IMG = 2048;
-  constexpr bool BNC = (LAYOUT & 2) != 0;
-  static_assert((LAYOUT & 1) == 0, "A must be k-contiguous");
-  __shared__ __attribute__((aligned(16))) float S[NST * 2 * IMG];
-  const int mt = p.M / BM, nt = p.N / BN;
-  int L;
-  {
-    const int nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-    L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  }
-  const int tn_ = L % nt, tm_ = (L / nt) % mt, g = L / (nt * mt);
-  const int m0 = tm_ * BM, n0 = tn_ * BN;
-  const float* __restrict__ A = p.A + g * p.ga;
-  const float* __restrict__ B = p.B + g * p.gb;
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int li = lane & 31, h = lane >> 5;
-  const int wm = (w >> 1) * 32, wn = (w & 1) * 32;
-  const int K = p.K;
-  const float* asrc[2];
-  const float* bsrc[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int d = 2 * w + i, row = 8 * d + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-    asrc[i] = A + (p.a_rows ? p.a_rows[m0 + row] : (int64_t)(m0 + row)) * p.lda + 4 * chunk;
-    if constexpr (!BNC) bsrc[i] = B + (int64_t)(n0 + row) * p.ldb + 4 * chunk;
-    else bsrc[i] = B + (int64_t)(4 * d + (lane >> 4)) * p.ldb + n0 + 4 * (lane & 15);
-  }
-  const uint32_t s_lds = (uint32_t)(uintptr_t)(lds_ptr_t)S;
-  auto dma = [&](const float* src, uint32_t lds_off) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(src), "s"(lds_off)
-                 : "memory");
-  };
-  auto issue = [&](int st, int k0) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const uint32_t base =
-          __builtin_amdgcn_readfirstlane(s_lds + (uint32_t)((st * 2 * IMG + (2 * w + i) * 256) * 4));
-      dma(asrc[i] + k0, base);
-      dma(BNC ? bsrc[i] + (int64_t)k0 * p.ldb : bsrc[i] + k0, base + IMG * 4);
-    }
-  };
-  float xaux[16];
-  if constexpr (epi_aux(EPI)) {
-    const float* __restrict__ ax = p.aux + g * p.gaux;
-    const int col = n0 + wn + li;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * h;
-      xaux[r] = ax[(int64_t)row * p.ld_aux + col];
-    }
-  }
-  f32x16 acc, acc2;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = acc2[r] = 0.f;
-  const int ns = K / BKD;
-  issue(0, 0);
-  if (ns > 1) issue(1, BKD);
-  const int ai = wm + li, aswz = (ai >> 1) & 7;
-  const int bi = wn + li, bswz = (bi >> 1) & 7;
-  for (int s = 0; s < ns; ++s) {
-    if (s + 1 < ns) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (s + 2 < ns) issue((s + 2) % NST, (s + 2) * BKD);
-    const float* As = S + (s % NST) * 2 * IMG;
-    const float* Bs = As + IMG;
-    float a[16], b[16];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 v = *reinterpret_cast<const float4*>(As + ai * 32 + 4 * ((4 * h + q) ^ aswz));
-      a[4 * q] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
-    }
-    if constexpr (!BNC) {
+    } else if constexpr (!BNC) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float4 v = *reinterpret_cast<const float4*>(Bs + bi * 32 + 4 * ((4 * h + q) ^ bswz));
@@ -587,13 +533,13 @@ __global__ __launch_bounds__(GTHREADS) void gemm_glds32_kernel(GemmP p) {
       }
     } else {
 #pragma unroll
-      for (int t = 0; t < 16; ++t) b[t] = Bs[(16 * h + t) * BN + bi];
+      for (int t = 0; t < BKD / 2; ++t) b[t] = Bs[(BKD / 2 * h + t) * BN + bi];
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int t = 0; t < 16; ++t) {
+    for (int t = 0; t < BKD / 2; ++t) {
       if (t & 1) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b[t], acc2, 0, 0, 0);
       else acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b[t], acc, 0, 0, 0);
     }
@@ -607,15 +553,7 @@ __global__ __launch_bounds__(GTHREADS) void gemm_glds32_kernel(GemmP p) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * h;
-    float v = acc[r] + acc2[r];
-    if constexpr (EPI == EPI_BIAS) v += bj;
-    if constexpr (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
-          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
-    if constexpr (epi_aux(EPI)) {
-      const float x = xaux[r];
-      v = EPI == EPI_DTANH ? v * (1.f - x * x) : (x > 0.f ? v : v * (x + 1.f));
-    }
-    C[(int64_t)row * p.ldc + col] = v;
+    C[(int64_t)row * p.ldc + col] = epi_apply<EPI>(acc[r] + acc2[r], bj, epi_aux(EPI) ? xaux[r] : 0.f);
   }
 }
 
@@ -695,9 +633,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_thin_kernel(GemmP p) {
         v += red[r * 64 + lane];
         v += red[(16 + r) * 64 + lane];
         v += red[(32 + r) * 64 + lane];
-        if constexpr (EPI == EPI_BIAS) v += bj;
-        if constexpr (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
-          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
+        v = epi_apply<EPI>(v, bj, 0.f);
         const int orow = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
         if (colv && orow < M) C[(int64_t)orow * p.ldc + li] = v;
       }
@@ -788,9 +724,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_thin16_kernel(GemmP p) {
           v += red[(4 * cb + r) * 64 + lane];
           v += red[(8 + 4 * cb + r) * 64 + lane];
           v += red[(16 + 4 * cb + r) * 64 + lane];
-          if constexpr (EPI == EPI_BIAS) v += bj;
-          if constexpr (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
-          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
+          v = epi_apply<EPI>(v, bj, 0.f);
           const int orow = t * 16 + 4 * h + r;
           if (col < N && orow < M) C[(int64_t)orow * p.ldc + col] = v;
         }
@@ -802,10 +736,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_thin16_kernel(GemmP p) {
 
 // (LRL_THIN16=0, or bit 5 of lrl_debug_gemm_paths: development switch back to the 32-row tiles)
 static bool thin16_enabled() {
-  static const int on = [] {
-    const char* e = getenv("LRL_THIN16");
-    return e && e[0] == '0' ? 0 : 1;
-  }();
+  static const int on = env_switch("LRL_THIN16", 1);
   return on != 0 && !(path_off() & 32);
 }
 
@@ -1045,6 +976,19 @@ __device__ __forceinline__ int x6_off(int r, int c) { return r * XBK + 8 * (c ^ 
 
 typedef short bf16x8_t __attribute__((ext_vector_type(8)));
 
+// One 32x32x16 step of the split product: c + a b from the hi / mid / lo planes a[0..2], b[0..2], as the six products
+// a2 b0, a1 b1, a0 b2, a1 b0, a0 b1, a0 b0 (smallest first) chained through c.  Every x6 family (x6, x6p, x6t, x6d)
+// takes its step from here over the same k order: that one order is what makes their results bit-identical.
+__device__ __forceinline__ f32x16 x6_mma(const bf16x8_t (&a)[3], const bf16x8_t (&b)[3], f32x16 c) {
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
+  return c;
+}
+
 template <int R, bool KC, bool KGATHER = false>
 struct X6Op {
   static constexpr int PLANE = R * XBK;                 // bf16 elements of one plane image
@@ -1196,7 +1140,7 @@ __global__ __launch_bounds__(GTHREADS, 3) void gemm_x6_kernel(GemmP p) {  // 3 w
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
   using OA = decltype(oa);
   using OB = decltype(ob);
-  // one k-step of the 32x32x16 products on the stage at As: six MFMAs per tile (smallest products first)
+  // one k-step of the 32x32x16 products on the stage at As
   auto compute = [&](const uint16_t* As) {
     const uint16_t* Bs = As + 3 * PA;
     bf16x8_t a[TM][3], b[TN][3];
@@ -1213,16 +1157,7 @@ __global__ __launch_bounds__(GTHREADS, 3) void gemm_x6_kernel(GemmP p) {  // 3 w
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        f32x16 c = acc[i][j];
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][2], b[j][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][0], c, 0, 0, 0);
-        acc[i][j] = c;
-      }
+      for (int j = 0; j < TN; ++j) acc[i][j] = x6_mma(a[i], b[j], acc[i][j]);
   };
   if constexpr (LRL_X6_PIPE && FAST) {
   // Software pipeline: slice s + 1 waits split-ready in registers while slice s is multiplied, so its split (VALU)
@@ -1341,17 +1276,7 @@ __global__ __launch_bounds__(GTHREADS, 3) void gemm_x6_kernel(GemmP p) {  // 3 w
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          if (FAST || row0 + r < p.M) {
-            float v = acc[i][j][4 * q + r];
-            if (EPI == EPI_BIAS) v += bj;
-            if (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
-          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
-            if constexpr (epi_aux(EPI)) {
-              const float x = xa[r];
-              v = EPI == EPI_DTANH ? v * (1.f - x * x) : (x > 0.f ? v : v * (x + 1.f));
-            }
-            crow[r * ldc] = v;
-          }
+          if (FAST || row0 + r < p.M) crow[r * ldc] = epi_apply<EPI>(acc[i][j][4 * q + r], bj, epi_aux(EPI) ? xa[r] : 0.f);
         }
         asm volatile("" ::: "memory");  // (bounds the epilogue's live loads and addresses to one row group)
       }
@@ -1380,38 +1305,31 @@ static int launch_x6_tile(const GemmP& p, int layout, int epi, int groups, hipSt
   const bool interior = p.M % BM == 0 && p.N % BN == 0 && p.K % XBK == 0 && p.kps % XBK == 0 &&
                         (!akc || p.avec == 4) && (!bkc || p.bvec == 4);
   const bool bg = p.b_rows != nullptr;
-#define LRL_X6G(L, E, G)                                                                                     \
-  do {                                                                                                       \
-    if (interior) hipLaunchKernelGGL((gemm_x6_kernel<BM, BN, L, E, true, G>), grid, dim3(GTHREADS), 0, st, p); \
-    else hipLaunchKernelGGL((gemm_x6_kernel<BM, BN, L, E, false, G>), grid, dim3(GTHREADS), 0, st, p);        \
-  } while (0)
-#define LRL_X6(L, E) LRL_X6G(L, E, false)
-  if (layout == GEMM_NT) {
-    if (epi == EPI_STORE) LRL_X6(GEMM_NT, EPI_STORE);
-    else if (epi == EPI_BIAS) LRL_X6(GEMM_NT, EPI_BIAS);
-    else if (epi == EPI_BIAS_ELU) LRL_X6(GEMM_NT, EPI_BIAS_ELU);
-    else if (epi == EPI_BIAS_TANH) LRL_X6(GEMM_NT, EPI_BIAS_TANH);
-    else return LRL_E_INVALID;
-  } else if (layout == GEMM_NN) {
-    if (epi == EPI_STORE) LRL_X6(GEMM_NN, EPI_STORE);
-    else if (epi == EPI_DELU) LRL_X6(GEMM_NN, EPI_DELU);
-    else if (epi == EPI_DTANH) LRL_X6(GEMM_NN, EPI_DTANH);
-    else return LRL_E_INVALID;
-  } else if (layout == GEMM_TN && epi == EPI_PARTIAL) {
+  if (layout == GEMM_TN) {  // (EPI_PARTIAL: try_x6 passes nothing else)
+    auto tn = [&](auto F, auto G, auto T) {
+      hipLaunchKernelGGL((gemm_x6_kernel<BM, BN, GEMM_TN, EPI_PARTIAL, F(), G(), T()>), grid, dim3(GTHREADS), 0, st, p);
+    };
+    const std::true_type yes;
+    const std::false_type no;
+    // the tagged symbols are the interior, full-size tile's (the tag is 0 elsewhere)
     const int tag = (BM == 128 && BN == 128 && interior) ? tn_shape_tag(p.M, p.N, groups) : 0;
-#define LRL_X6T(G, T) hipLaunchKernelGGL((gemm_x6_kernel<BM, BN, GEMM_TN, EPI_PARTIAL, true, G, T>), grid, dim3(GTHREADS), 0, st, p)
-    if (tag == 1) LRL_X6T(false, 1);
-    else if (tag == 2) LRL_X6T(false, 2);
-    else if (tag == 4) { if (bg) LRL_X6T(true, 4); else LRL_X6T(false, 4); }
-    else if (tag == 6) LRL_X6T(false, 6);
-    else if (bg) LRL_X6G(GEMM_TN, EPI_PARTIAL, true);
-    else LRL_X6G(GEMM_TN, EPI_PARTIAL, false);
-#undef LRL_X6T
+    if (tag == 1) tn(yes, no, Int<1>{});
+    else if (tag == 2) tn(yes, no, Int<2>{});
+    else if (tag == 4 && bg) tn(yes, yes, Int<4>{});
+    else if (tag == 4) tn(yes, no, Int<4>{});
+    else if (tag == 6) tn(yes, no, Int<6>{});
+    else if (interior && bg) tn(yes, yes, Int<0>{});
+    else if (interior) tn(yes, no, Int<0>{});
+    else if (bg) tn(no, yes, Int<0>{});
+    else tn(no, no, Int<0>{});
   } else {
-    return LRL_E_INVALID;
+    const int rc = with_pair(layout, epi, BatchMajor{}, [&](auto L, auto E) {
+      if (interior) hipLaunchKernelGGL((gemm_x6_kernel<BM, BN, L(), E(), true, false>), grid, dim3(GTHREADS), 0, st, p);
+      else hipLaunchKernelGGL((gemm_x6_kernel<BM, BN, L(), E(), false, false>), grid, dim3(GTHREADS), 0, st, p);
+      return 0;
+    });
+    if (rc) return rc;
   }
-#undef LRL_X6
-#undef LRL_X6G
   note_path(FAM_X6, BM, BN, interior);
   return hipGetLastError() == hipSuccess ? 0 : LRL_E_HIP;
 }
@@ -1419,10 +1337,7 @@ static int launch_x6_tile(const GemmP& p, int layout, int epi, int groups, hipSt
 // bf16-split switch: LRL_GEMM_X6=0 (or bit 4 of lrl_debug_gemm_paths) keeps every product on the fp32 MFMA kernels
 // (A/B comparisons): no x6, x6d or x6t, and no x6p unless the caller itself hands planes over
 static bool x6_enabled() {
-  static const int on = [] {
-    const char* e = getenv("LRL_GEMM_X6");
-    return e && e[0] == '0' ? 0 : 1;
-  }();
+  static const int on = env_switch("LRL_GEMM_X6", 1);
   return on != 0 && !(path_off() & 16);
 }
 
@@ -1484,8 +1399,8 @@ static int try_x6(const GemmP& p, int layout, int epi, int groups, hipStream_t s
 //   wave-instruction fills 16 rows (lane l: row l / 4, slot l % 4, source chunk pre-swizzled).
 //   B images per stage: 3 planes of [128][16] bf16 (32-B rows), chunk c of row r in slot c ^ ((r >> 3) & 1); a DMA
 //   wave-instruction fills 32 rows of one plane.
-// Tile BM x 128 (BM = 64 / 128), 4 waves in a 2 x 2 grid, wave tile (BM/2) x 64; the six MFMA products per 32x32x16
-// step in the order of gemm_x6_kernel over the same k order, so the result is bit-identical to it.
+// Tile BM x 128 (BM = 64 / 128), 4 waves in a 2 x 2 grid, wave tile (BM/2) x 64; x6_mma steps over gemm_x6_kernel's k
+// order.
 template <int BM, int EPI, bool GATHER>
 __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6p_kernel(GemmP p) {
   constexpr int BN = 128, NST = 3, TM = BM / 64, TN = 2;
@@ -1587,16 +1502,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6p_kernel(GemmP p) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        f32x16 c = acc[i][j];
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][2], b[j][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][0], c, 0, 0, 0);
-        acc[i][j] = c;
-      }
+      for (int j = 0; j < TN; ++j) acc[i][j] = x6_mma(a[i], b[j], acc[i][j]);
   }
 
   float* __restrict__ C = p.C + g * p.gc;
@@ -1620,17 +1526,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6p_kernel(GemmP p) {
           for (int r = 0; r < 4; ++r) xa[r] = xrow[r * p.ld_aux];
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float v = acc[i][j][4 * q + r];
-          if (EPI == EPI_BIAS) v += bj;
-          if (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
-          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
-          if constexpr (epi_aux(EPI)) {
-            const float x = xa[r];
-            v = EPI == EPI_DTANH ? v * (1.f - x * x) : (x > 0.f ? v : v * (x + 1.f));
-          }
-          crow[r * p.ldc] = v;
-        }
+        for (int r = 0; r < 4; ++r) crow[r * p.ldc] = epi_apply<EPI>(acc[i][j][4 * q + r], bj, epi_aux(EPI) ? xa[r] : 0.f);
       }
   }
 }
@@ -1641,8 +1537,8 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6p_kernel(GemmP p) {
 // k-rows; 16-B chunk c of k-row k sits in slot c ^ (8 * ((k >> 3) & 1)), so the two lane halves of a read, k and
 // k + 8, use opposite bank halves), in a 3-deep ring with counted vmcnt and a raw barrier.  Each lane gathers its
 // 8 k-values per MFMA operand with ds_read_b32 (immediate offsets) and splits them in registers.  128 x 128 tiles,
-// 4 waves of 2 x 2 MFMA tiles, the six products in gemm_x6_kernel's order over the same k order, and the bias
-// gradient partial summed in its (row, k-half) order: bit-identical to it.
+// 4 waves of 2 x 2 MFMA tiles, x6_mma steps over gemm_x6_kernel's k order, and the bias gradient partial summed in its
+// (row, k-half) order.
 constexpr int X6T_MAX_GATHER_KPS = 1024;  // gathered-B splits of at most this many rows (the row list in LDS)
 template <int BN, int TAG, bool BGATHER>
 __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6t_kernel(GemmP p) {
@@ -1766,16 +1662,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6t_kernel(GemmP p) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        f32x16 c = acc[i][j];
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][2], b[j][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][0], c, 0, 0, 0);
-        acc[i][j] = c;
-      }
+      for (int j = 0; j < TN; ++j) acc[i][j] = x6_mma(a[i], b[j], acc[i][j]);
   }
 
   float* __restrict__ C = p.C + g * p.gc + (int64_t)sp * p.part_stride;
@@ -1817,8 +1704,8 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6t_kernel(GemmP p) {
 // barrier, two stages in flight across it); each lane reads its 8 k-values per MFMA operand and splits them in
 // registers.  k-contiguous operands (A; B of NT): [R][16] images (64-B rows, 16-B chunk c of row r in slot
 // c ^ ((r >> 2) & 3)), read with two ds_read_b128; the n-contiguous B of NN: [16][BN] (chunk c of k-row k in slot
-// c ^ (8 * ((k >> 3) & 1))), read with ds_read_b32.  Tile shapes as gemm_x6_kernel picks them; the six products in
-// its order over the same k order: bit-identical to it.
+// c ^ (8 * ((k >> 3) & 1))), read with ds_read_b32.  Tile shapes as gemm_x6_kernel picks them; x6_mma steps over its k
+// order.
 template <int BM, int BN, int LAYOUT, int EPI, bool GATHER>
 __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6d_kernel(GemmP p) {
   constexpr bool BNC = LAYOUT == GEMM_NN;
@@ -1941,16 +1828,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6d_kernel(GemmP p) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        f32x16 c = acc[i][j];
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][2], b[j][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][0], c, 0, 0, 0);
-        acc[i][j] = c;
-      }
+      for (int j = 0; j < TN; ++j) acc[i][j] = x6_mma(a[i], b[j], acc[i][j]);
   }
 
   float* __restrict__ C = p.C + g * p.gc;
@@ -1964,7 +1842,7 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6d_kernel(GemmP p) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
+      for (int q = 0; q < 4; ++q) {  // rows 8q + 4h .. +3 of the MFMA tile: accumulator registers 4q .. 4q+3
         const int row0 = m0 + wm + 32 * i + 8 * q + 4 * h;
         float* __restrict__ crow = C + (int64_t)row0 * p.ldc + col;
         float xa[4];
@@ -1974,41 +1852,20 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6d_kernel(GemmP p) {
           for (int r = 0; r < 4; ++r) xa[r] = xrow[r * p.ld_aux];
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float v = acc[i][j][4 * q + r];
-          if (EPI == EPI_BIAS) v += bj;
-          if (EPI == EPI_BIAS_ELU) v = elu_f(v + bj);
-          if constexpr (EPI == EPI_BIAS_TANH) v = tanh_f(v + bj);
-          if constexpr (epi_aux(EPI)) {
-            const float x = xa[r];
-            v = EPI == EPI_DTANH ? v * (1.f - x * x) : (x > 0.f ? v : v * (x + 1.f));
-          }
-          crow[r * p.ldc] = v;
-        }
+        for (int r = 0; r < 4; ++r) crow[r * p.ldc] = epi_apply<EPI>(acc[i][j][4 * q + r], bj, epi_aux(EPI) ? xa[r] : 0.f);
       }
   }
 }
 
+// the offered epilogues of LAYOUT only (Offered): no instantiation for a pair that cannot be reached
 template <int BM, int BN, int LAYOUT>
-static void launch_x6d_l(const GemmP& p, int epi, int groups, hipStream_t st) {
+static int launch_x6d_l(const GemmP& p, int epi, int groups, hipStream_t st) {
   dim3 grid((unsigned)((p.M / BM) * (p.N / BN) * groups));
-  const bool gat = p.a_rows != nullptr;
-#define LRL_X6D(E)                                                                                             \
-  do {                                                                                                         \
-    if (gat) hipLaunchKernelGGL((gemm_x6d_kernel<BM, BN, LAYOUT, E, true>), grid, dim3(GTHREADS), 0, st, p);   \
-    else hipLaunchKernelGGL((gemm_x6d_kernel<BM, BN, LAYOUT, E, false>), grid, dim3(GTHREADS), 0, st, p);      \
-  } while (0)
-  if (LAYOUT == GEMM_NT) {
-    if (epi == EPI_STORE) LRL_X6D(EPI_STORE);
-    else if (epi == EPI_BIAS) LRL_X6D(EPI_BIAS);
-    else if (epi == EPI_BIAS_TANH) LRL_X6D(EPI_BIAS_TANH);
-    else LRL_X6D(EPI_BIAS_ELU);
-  } else {
-    if (epi == EPI_STORE) LRL_X6D(EPI_STORE);
-    else if (epi == EPI_DTANH) LRL_X6D(EPI_DTANH);
-    else LRL_X6D(EPI_DELU);
-  }
-#undef LRL_X6D
+  return with_int(epi, typename Offered<LAYOUT, false>::epis{}, [&](auto E) {
+    if (p.a_rows) hipLaunchKernelGGL((gemm_x6d_kernel<BM, BN, LAYOUT, E(), true>), grid, dim3(GTHREADS), 0, st, p);
+    else hipLaunchKernelGGL((gemm_x6d_kernel<BM, BN, LAYOUT, E(), false>), grid, dim3(GTHREADS), 0, st, p);
+    return 0;
+  });
 }
 
 // x6d path switch, off by default: measured 1.00-1.05x gemm_x6_kernel on the backward-data products in isolation but
@@ -2016,10 +1873,7 @@ static void launch_x6d_l(const GemmP& p, int epi, int groups, hipStream_t st) {
 // the forward ones, whose float4-staged operands gemm_x6_kernel splits once per workgroup instead of once per reading
 // wave (profiles/r4n_x6d_vs_x6.jsonl).  LRL_GEMM_X6D=1: the backward-data products, =2: the forward too
 static int x6d_mode() {
-  static const int m = [] {
-    const char* e = getenv("LRL_GEMM_X6D");
-    return e ? atoi(e) : 0;
-  }();
+  static const int m = env_switch("LRL_GEMM_X6D", 0);
   const int off = path_off();
   return (off & 4) ? 0 : (off & 8) ? 2 : m;
 }
@@ -2029,30 +1883,22 @@ static bool x6d_enabled() { return x6d_mode() != 0; }
 static int try_x6d(const GemmP& p, int layout, int epi, int groups, int bm, int bn, hipStream_t st) {
   if (!x6d_enabled() || (layout != GEMM_NT && layout != GEMM_NN) || p.splits != 1) return 0;
   if (layout == GEMM_NT && x6d_mode() != 2) return 0;
-  if (layout == GEMM_NT && epi != EPI_STORE && !epi_bias(epi)) return 0;
-  if (layout == GEMM_NN && epi != EPI_STORE && !epi_aux(epi)) return 0;
   if (p.M % bm || p.N % bn || p.K % 16 || p.K < 32 || p.avec != 4 || p.bvec != 4) return 0;
   if (layout == GEMM_NN && p.b_rows) return 0;
-  const int key = (bm == 128 ? 2 : 0) | (bn == 128 ? 1 : 0) | (layout == GEMM_NN ? 4 : 0);
-  switch (key) {
-    case 0: launch_x6d_l<64, 64, GEMM_NT>(p, epi, groups, st); break;
-    case 1: launch_x6d_l<64, 128, GEMM_NT>(p, epi, groups, st); break;
-    case 2: launch_x6d_l<128, 64, GEMM_NT>(p, epi, groups, st); break;
-    case 3: launch_x6d_l<128, 128, GEMM_NT>(p, epi, groups, st); break;
-    case 4: launch_x6d_l<64, 64, GEMM_NN>(p, epi, groups, st); break;
-    case 5: launch_x6d_l<64, 128, GEMM_NN>(p, epi, groups, st); break;
-    case 6: launch_x6d_l<128, 64, GEMM_NN>(p, epi, groups, st); break;
-    default: launch_x6d_l<128, 128, GEMM_NN>(p, epi, groups, st); break;
-  }
+  const int rc = with_int(layout, BatchMajor{}, [&](auto L) {
+    constexpr int LAYOUT = decltype(L)::value;
+    if (bm == 128 && bn == 128) return launch_x6d_l<128, 128, LAYOUT>(p, epi, groups, st);
+    if (bm == 128) return launch_x6d_l<128, 64, LAYOUT>(p, epi, groups, st);
+    if (bn == 128) return launch_x6d_l<64, 128, LAYOUT>(p, epi, groups, st);
+    return launch_x6d_l<64, 64, LAYOUT>(p, epi, groups, st);
+  });
+  if (rc) return rc;
   note_path(FAM_X6D, bm, bn);
   return hipGetLastError() == hipSuccess ? 1 : LRL_E_HIP;
 }
 // x6t path switch: LRL_GEMM_X6T=0 keeps the weight gradients on gemm_x6_kernel
 static bool x6t_enabled() {
-  static const int on = [] {
-    const char* e = getenv("LRL_GEMM_X6T");
-    return e && e[0] == '0' ? 0 : 1;
-  }();
+  static const int on = env_switch("LRL_GEMM_X6T", 1);
   return on != 0 && x6_enabled() && !(path_off() & 2);
 }
 
@@ -2089,11 +1935,8 @@ static int try_x6t(const GemmP& p, int layout, int epi, int groups, hipStream_t 
 // shape (the 6-byte planes of B cost more DMA issue and LDS traffic than the staging split saves, and A
 // is split by both waves that read it); products whose caller hands over planes (lrl_gemm_f32 layout | 0x100) run it
 static bool x6p_enabled() {
-  static const int on = [] {
-    const char* e = getenv("LRL_GEMM_X6P");
-    return e && e[0] == '1' ? 1 : 0;
-  }();
-  return on != 0 && x6_enabled() && !(path_off() & 1);
+  static const int on = env_switch("LRL_GEMM_X6P", 0);
+  return on == 1 && x6_enabled() && !(path_off() & 1);
 }
 
 bool gemm_x6p_enabled() { return x6p_enabled(); }
@@ -2103,7 +1946,7 @@ static int try_x6p(const GemmP& p, int layout, int epi, int groups, hipStream_t 
   if (!p.bpl || (path_off() & 1) || (layout != GEMM_NT && layout != GEMM_NN) ||
       p.splits != 1)
     return 0;
-  if (epi != EPI_STORE && !epi_bias(epi) && !epi_aux(epi)) return 0;
+  if (epi == EPI_PARTIAL) return 0;
   if (p.M % 64 || p.N % 128 || p.K % 16 || p.K < 32 || p.avec != 4 || p.bpl_ld != p.K) return 0;
   if ((reinterpret_cast<uintptr_t>(p.bpl) & 15) || p.gbp % 8 || p.bpl_ps % 8) return 0;
   // 128-row tiles when they give at least three per CU pair of workgroup slots, 64 otherwise
@@ -2111,26 +1954,15 @@ static int try_x6p(const GemmP& p, int layout, int epi, int groups, hipStream_t 
   const bool big = p.M % 128 == 0 && t128 >= 768;
   const bool gat = p.a_rows != nullptr;
   dim3 grid((unsigned)((p.M / (big ? 128 : 64)) * (p.N / 128) * groups));
-#define LRL_X6P(BMV, E)                                                                                         \
-  do {                                                                                                          \
-    if (gat) hipLaunchKernelGGL((gemm_x6p_kernel<BMV, E, true>), grid, dim3(GTHREADS), 0, st, p);              \
-    else hipLaunchKernelGGL((gemm_x6p_kernel<BMV, E, false>), grid, dim3(GTHREADS), 0, st, p);                 \
-  } while (0)
-#define LRL_X6P_E(E)      \
-  do {                    \
-    if (big) LRL_X6P(128, E); \
-    else LRL_X6P(64, E);  \
-  } while (0)
-  switch (epi) {
-    case EPI_STORE: LRL_X6P_E(EPI_STORE); break;
-    case EPI_BIAS: LRL_X6P_E(EPI_BIAS); break;
-    case EPI_BIAS_ELU: LRL_X6P_E(EPI_BIAS_ELU); break;
-    case EPI_BIAS_TANH: LRL_X6P_E(EPI_BIAS_TANH); break;
-    case EPI_DTANH: LRL_X6P_E(EPI_DTANH); break;
-    default: LRL_X6P_E(EPI_DELU); break;
-  }
-#undef LRL_X6P_E
-#undef LRL_X6P
+  // (the kernel has no layout parameter: op(B) is already in [n][k] planes)
+  const int rc = with_pair(layout, epi, BatchMajor{}, [&](auto, auto E) {
+    if (big && gat) hipLaunchKernelGGL((gemm_x6p_kernel<128, E(), true>), grid, dim3(GTHREADS), 0, st, p);
+    else if (big) hipLaunchKernelGGL((gemm_x6p_kernel<128, E(), false>), grid, dim3(GTHREADS), 0, st, p);
+    else if (gat) hipLaunchKernelGGL((gemm_x6p_kernel<64, E(), true>), grid, dim3(GTHREADS), 0, st, p);
+    else hipLaunchKernelGGL((gemm_x6p_kernel<64, E(), false>), grid, dim3(GTHREADS), 0, st, p);
+    return 0;
+  });
+  if (rc) return rc;
   note_path(FAM_X6P, big ? 128 : 64, 128);
   return hipGetLastError() == hipSuccess ? 1 : LRL_E_HIP;
 }
@@ -2187,33 +2019,10 @@ int x6_planes_launch(const PlaneJob* jobs, int n, void* stream) {
 
 template <int BM, int BN>
 static int launch_bm(const GemmP& p, int layout, int epi, dim3 grid, hipStream_t st) {
-#define LRL_GEMM_LAUNCH(L, E) hipLaunchKernelGGL((gemm_kernel<BM, BN, L, E>), grid, dim3(GTHREADS), 0, st, p)
-  switch (layout) {
-    case GEMM_NT:
-      switch (epi) {
-        case EPI_STORE: LRL_GEMM_LAUNCH(GEMM_NT, EPI_STORE); return 0;
-        case EPI_BIAS: LRL_GEMM_LAUNCH(GEMM_NT, EPI_BIAS); return 0;
-        case EPI_BIAS_ELU: LRL_GEMM_LAUNCH(GEMM_NT, EPI_BIAS_ELU); return 0;
-        case EPI_BIAS_TANH: LRL_GEMM_LAUNCH(GEMM_NT, EPI_BIAS_TANH); return 0;
-      }
-      break;
-    case GEMM_NN:
-      switch (epi) {
-        case EPI_STORE: LRL_GEMM_LAUNCH(GEMM_NN, EPI_STORE); return 0;
-        case EPI_DELU: LRL_GEMM_LAUNCH(GEMM_NN, EPI_DELU); return 0;
-        case EPI_DTANH: LRL_GEMM_LAUNCH(GEMM_NN, EPI_DTANH); return 0;
-        case EPI_PARTIAL: LRL_GEMM_LAUNCH(GEMM_NN, EPI_PARTIAL); return 0;
-      }
-      break;
-    case GEMM_TN:
-      if (epi == EPI_PARTIAL) {
-        LRL_GEMM_LAUNCH(GEMM_TN, EPI_PARTIAL);
-        return 0;
-      }
-      break;
-  }
-#undef LRL_GEMM_LAUNCH
-  return LRL_E_INVALID;
+  return with_pair<true>(layout, epi, AnyLayout{}, [&](auto L, auto E) {
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, L(), E()>), grid, dim3(GTHREADS), 0, st, p);
+    return 0;
+  });
 }
 
 // widest staging access allowed by the pitch / base / group offset alignment of an operand
@@ -2265,10 +2074,10 @@ int gemm_last_path() { return g_last_path; }
 int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) {
   GemmP p = p0;
   if (p.M <= 0 || p.N <= 0 || p.K < 0 || groups <= 0) return LRL_E_INVALID;
-  // the tanh epilogues exist for the forward (NT) and backward-data (NN) products only: any other pairing is refused
-  // here, before a family's launcher could default it to an ELU instantiation
-  if ((epi == EPI_BIAS_TANH && layout != GEMM_NT) || (epi == EPI_DTANH && layout != GEMM_NN)) return LRL_E_INVALID;
-  if (epi == EPI_DTANH && !p.aux) return LRL_E_INVALID;
+  // a pair outside the table (Offered) is refused here, in front of every family, whatever the shape and the switches;
+  // so is the tanh backward without its aux operand
+  if (with_pair<true>(layout, epi, AnyLayout{}, [](auto, auto) { return 0; }) || (epi == EPI_DTANH && !p.aux))
+    return LRL_E_INVALID;
   if (p.splits <= 0) p.splits = 1;
   if (p.kps <= 0) p.kps = (p.K + p.splits - 1) / p.splits;
   p.kps = (p.kps + GBK - 1) / GBK * GBK;
@@ -2297,22 +2106,12 @@ int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) 
 #define LRL_GLDS_BK32 1
 #endif
     const bool bk32 = LRL_GLDS_BK32 && p.K % 32 == 0 && p.K >= 64;
-#define LRL_GLDS(L, E)                                                                      \
-  do {                                                                                      \
-    if (bk32) hipLaunchKernelGGL((gemm_glds32_kernel<L, E>), g1, dim3(GTHREADS), 0, st, p); \
-    else hipLaunchKernelGGL((gemm_glds_kernel<L, E>), g1, dim3(GTHREADS), 0, st, p);        \
-  } while (0)
-    if (layout == GEMM_NT) {
-      if (epi == EPI_STORE) LRL_GLDS(GEMM_NT, EPI_STORE);
-      else if (epi == EPI_BIAS) LRL_GLDS(GEMM_NT, EPI_BIAS);
-      else if (epi == EPI_BIAS_TANH) LRL_GLDS(GEMM_NT, EPI_BIAS_TANH);
-      else LRL_GLDS(GEMM_NT, EPI_BIAS_ELU);
-    } else {
-      if (epi == EPI_STORE) LRL_GLDS(GEMM_NN, EPI_STORE);
-      else if (epi == EPI_DTANH) LRL_GLDS(GEMM_NN, EPI_DTANH);
-      else LRL_GLDS(GEMM_NN, EPI_DELU);
-    }
-#undef LRL_GLDS
+    const int rc = with_pair(layout, epi, BatchMajor{}, [&](auto L, auto E) {
+      if (bk32) hipLaunchKernelGGL((gemm_glds_kernel<L(), E(), 32>), g1, dim3(GTHREADS), 0, st, p);
+      else hipLaunchKernelGGL((gemm_glds_kernel<L(), E(), 16>), g1, dim3(GTHREADS), 0, st, p);
+      return 0;
+    });
+    if (rc) return rc;
     note_path(bk32 ? FAM_GLDS32 : FAM_GLDS, 64, 64);
     return hipGetLastError() == hipSuccess ? 0 : LRL_E_HIP;
   }
@@ -2331,17 +2130,11 @@ int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) 
   if (layout != GEMM_TN && p.splits == 1 && p.N <= 32 && p.K % 128 == 0 && p.avec == 4 && p.M >= 256 &&
       (kb128 == 4 || kb128 == 8) &&  // (shorter k: the register-staged 128 x 32 tile is as fast)
       (epi == EPI_STORE || epi_bias(epi))) {
-    int trc = LRL_E_INVALID;
-    if (layout == GEMM_NT) {
-      if (epi == EPI_STORE) trc = launch_thin<GEMM_NT, EPI_STORE>(p, groups, st);
-      else if (epi == EPI_BIAS) trc = launch_thin<GEMM_NT, EPI_BIAS>(p, groups, st);
-      else if (epi == EPI_BIAS_TANH) trc = launch_thin<GEMM_NT, EPI_BIAS_TANH>(p, groups, st);
-      else trc = launch_thin<GEMM_NT, EPI_BIAS_ELU>(p, groups, st);
-    } else {
-      if (epi == EPI_STORE) trc = launch_thin<GEMM_NN, EPI_STORE>(p, groups, st);
-      else if (epi == EPI_BIAS) trc = launch_thin<GEMM_NN, EPI_BIAS>(p, groups, st);
-      else trc = launch_thin<GEMM_NN, EPI_BIAS_ELU>(p, groups, st);
-    }
+    // (the condition above leaves NN its store epilogue only: the thin kernels have no aux operand)
+    const int trc = with_pair(layout, epi, BatchMajor{}, [&](auto L, auto E) {
+      if constexpr (epi_aux(decltype(E)::value)) return LRL_E_INVALID;
+      else return launch_thin<L(), E()>(p, groups, st);
+    });
     if (trc) return trc;
     return hipGetLastError() == hipSuccess ? 0 : LRL_E_HIP;
   }

@@ -449,6 +449,46 @@ def test_every_family_is_reached(fam):
     assert tiles
 
 
+# a shape and switch setting that would reach each family: (family, M, N, K, mask, planes)
+UNOFFERED_ROUTES = [("x6", 128, 128, 64, 0, False), ("x6d", 128, 128, 64, 8, False),
+                    ("glds32", 128, 128, 64, 16, False), ("glds", 128, 128, 48, 16, False),
+                    ("staged", 129, 70, 40, 16, False), ("thin16", 256, 24, 512, 0, False),
+                    ("thin32", 256, 24, 512, 32, False), ("x6p", 64, 128, 32, 0, True)]
+UNOFFERED_PAIRS = [(NT, 3), (NN, 1), (NN, 2)]
+
+
+@pytest.mark.parametrize("layout,epi", UNOFFERED_PAIRS, ids=["nt-e3", "nn-e1", "nn-e2"])
+@pytest.mark.parametrize("route", UNOFFERED_ROUTES, ids=[r[0] for r in UNOFFERED_ROUTES])
+def test_an_unoffered_pair_is_refused_in_front_of_every_family(route, layout, epi):
+    """A (layout, epilogue) pair outside the library's table is an error whatever family the shape and the switches
+    would pick, and nothing is written.  Bias and aux are real buffers of full extent: a dispatch mistake shows as a
+    return code of 0 or a touched output, never as a read through a null pointer."""
+    _, M, N, K, mask, planes = route
+    A = Buf(1, M, K, K, 0, 0, NAN_BITS)
+    B = Buf(1, N, K, K, 0, 0, NAN_BITS) if layout == NT else Buf(1, K, N, N, 0, 0, NAN_BITS)
+    bias, aux = Buf(1, 1, N, N, 0, 0, NAN_BITS), Buf(1, M, N, N, 0, 0, NAN_BITS)
+    for b in (A, B, bias, aux):
+        b.view.fill_(0.25)
+    out = Buf(1, M, N, N, 0, 0, SENT)
+    need = -(-3 * N * (-(-K // 16) * 16) // 2) if planes else 0
+    ws = torch.full((need + SLACK,), SENT, dtype=torch.int32, device=dev)
+    desc = _abi.LrlGemmDesc(layout=layout, epi=epi, M=M, N=N, K=K, groups=1, planes=int(planes), splits=0,
+                            A=A.ptr, B=B.ptr, C=out.ptr, bias=bias.ptr, aux=aux.ptr,
+                            workspace=ws.data_ptr() if planes else None, workspace_floats=need,
+                            lda=K, ldb=K if layout == NT else N, ldc=N, ld_aux=N)
+    lib = _abi.lib()
+    before = lib.lrl_debug_gemm_paths(C.c_int32(mask))
+    try:
+        rc = lib.lrl_gemm_f32_ex(C.byref(desc), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+    finally:
+        assert lib.lrl_debug_gemm_paths(C.c_int32(before)) == mask
+    assert rc != 0
+    assert bool((out.flat == SENT).all()), "a refused product wrote to its output"
+    assert bool((ws[need:] == SENT).all())
+    assert lib.lrl_debug_gemm_paths(C.c_int32(before)) == before   # the switches are as the test found them
+
+
 def test_an_empty_split_is_refused():
     """A split count that leaves a split without rows is an error (production never produces one), and nothing is
     written."""
