@@ -725,6 +725,16 @@ typedef struct lrl_gemm_desc {
 } lrl_gemm_desc;
 int32_t lrl_gemm_f32_ex(const lrl_gemm_desc* d, void* stream);
 
+/* Test entry point of the multi-problem launch the update's backward tail uses: the n (2 or 3) products d[0 .. n) run
+ * as ONE kernel whose grid is the concatenation of their own grids, d[0]'s workgroups first; each runs the kernel body,
+ * tile and split lrl_gemm_f32_ex would give it, so C, the partials and the bias partials in each workspace are
+ * bit-identical to n lrl_gemm_f32_ex calls.  One segmented reduction of every TN product follows.  The sets on offer,
+ * riders first and the large weight gradient (the host) last, are those of the preset networks:
+ * {ragged TN, thin-k NN + elu', TN host}, {TN, NN + elu', TN host}, {gathered thin TN, TN host}.  planes must be 0.
+ * Returns 0, 1 when the descriptors are not such a set (nothing was launched or written), or an error (< 0).
+ * path_out of the last descriptor receives the host's path report, splits_out of each its split count. */
+int32_t lrl_gemm_f32_multi(const lrl_gemm_desc* d, int32_t n, void* stream);
+
 /* reset_idx's episode logging (legged_robot.py:261-276) for `rows` rows of a [rows][ld] f32 device table at once:
  * means[r] = mean over the n env ids of table[r][ids] (fixed-order reduction), then, when `zero`, those entries are
  * set to 0 (the reset envs' episode sums).  One launch on `stream`; means is a device array of `rows` floats (NaN for

@@ -100,6 +100,20 @@ enum GemmLayout : int { GEMM_NT = 0, GEMM_NN = 2, GEMM_TN = 3 };
 // lrl error code (bad shape / unsupported layout).
 int gemm_launch(const GemmP& p, int layout, int epi, int groups, void* stream);
 
+// One product of a multi-problem launch: what gemm_launch takes.
+struct GemmJob {
+  GemmP p;
+  int layout, epi, groups;
+};
+constexpr int MAX_MULTI_JOBS = 3;
+// Enqueue 2 or 3 products that do not depend on each other as ONE kernel: its grid is the concatenation of the grids
+// gemm_launch would give the jobs, job 0's workgroups first, and every job runs the kernel body, tile and split of its
+// own launch, so each output is bit-identical to gemm_launch's.  The job sets on offer are those of the update's backward
+// tail, riders first and the large weight gradient (the host) last (lrl_gemm.hip, MultiCombos).  Returns 1 when
+// launched, 0 when the set is not one of them (nothing was launched: the caller launches the jobs one by one), or a
+// negative lrl error code.  gemm_last_path then reports the last job's family and tile.
+int gemm_launch_multi(const GemmJob* jobs, int n, void* stream);
+
 // Kernel family of a launch (the LRL_GEMM_PATH_* values of include/lrl.h)
 enum GemmFamily : int {
   FAM_NONE = 0, FAM_X6P = 1, FAM_X6T = 2, FAM_X6 = 3, FAM_X6D = 4, FAM_GLDS = 5, FAM_GLDS32 = 6, FAM_GLDS_TN = 7,

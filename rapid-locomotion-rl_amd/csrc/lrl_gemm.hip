@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <tuple>
 #include <type_traits>
 #include <cstdio>
 #include <cstdlib>
@@ -240,18 +241,24 @@ __device__ __forceinline__ void stage_store(float (*S)[R + PAD], const float4 (&
   }
 }
 
+// The kernel bodies that a multi-problem launch (gemm_launch_multi) can also run are device functions of
+// (problem, vblock, vgrid, smem): the workgroup's index within its problem's grid, that grid's size, and the base of the
+// workgroup's LDS block (Body::LDS bytes, 16-B aligned).  Their __global__ kernels are wrappers that pass blockIdx.x,
+// gridDim.x and a static array of that size.
 template <int BM, int BN, int LAYOUT, int EPI>
-__global__ __launch_bounds__(GTHREADS) void gemm_kernel(GemmP p) {
+__device__ __forceinline__ void gemm_staged_body(const GemmP& p, int vblock, int vgrid, uint8_t* smem) {
   using T = GemmTile<BM, BN, LAYOUT>;
-  __shared__ __attribute__((aligned(16))) float As[2][GBK][BM + T::PA];
-  __shared__ __attribute__((aligned(16))) float Bs[2][GBK][BN + T::PB];
+  typedef float AStage[GBK][BM + T::PA];
+  typedef float BStage[GBK][BN + T::PB];
+  AStage* As = reinterpret_cast<AStage*>(smem);                       // [2]
+  BStage* Bs = reinterpret_cast<BStage*>(smem + 2 * sizeof(AStage));  // [2]
   // XCD-aware tile order: the hardware deals workgroup ids round-robin over the 8 XCDs, so id i is
   // renumbered to L with consecutive L on the same XCD; L runs n-tile fastest, then m-tile, then
   // (group, split): the workgroups sharing an A row-panel (or a split's rows) share one XCD's L2.
   const int mt = (p.M + BM - 1) / BM, nt = (p.N + BN - 1) / BN;
   int L;
   {
-    const int nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
+    const int nwg = vgrid, orig = vblock, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
     L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
   }
   const int tn_ = L % nt, tm_ = (L / nt) % mt, zz = L / (nt * mt);
@@ -401,6 +408,21 @@ __global__ __launch_bounds__(GTHREADS) void gemm_kernel(GemmP p) {
   // bias partial layout [split][group][M] (contiguous per split, like the C partials)
   if (do_bsum && threadIdx.x < BM && m0 + (int)threadIdx.x < p.M)
     p.bias_part[((int64_t)s * groups + g) * p.M + m0 + threadIdx.x] = bsum;
+}
+template <int BM, int BN, int LAYOUT, int EPI>
+struct StagedBody {
+  using T = GemmTile<BM, BN, LAYOUT>;
+  static constexpr int LDS = 2 * GBK * (BM + T::PA + BN + T::PB) * (int)sizeof(float);
+  static_assert((2 * GBK * (BM + T::PA) * sizeof(float)) % 16 == 0, "B stages 16-B aligned");
+  static __device__ __forceinline__ void run(const GemmP& p, int vblock, int vgrid, uint8_t* smem) {
+    gemm_staged_body<BM, BN, LAYOUT, EPI>(p, vblock, vgrid, smem);
+  }
+};
+template <int BM, int BN, int LAYOUT, int EPI>
+__global__ __launch_bounds__(GTHREADS) void gemm_kernel(GemmP p) {
+  using Body = StagedBody<BM, BN, LAYOUT, EPI>;
+  __shared__ __attribute__((aligned(16))) uint8_t S[Body::LDS];
+  Body::run(p, blockIdx.x, gridDim.x, S);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1103,18 +1125,16 @@ struct X6Op {
   }
 };
 
-// TAG: trace tag only (the weight-gradient shape, tn_shape_tag): each of the update's large weight gradients gets its own
-// symbol so a kernel trace / PMC pass keys its launches apart; the code is the same for every value
-template <int BM, int BN, int LAYOUT, int EPI, bool FAST, bool BGATHER, int TAG = 0>
-__global__ __launch_bounds__(GTHREADS, 3) void gemm_x6_kernel(GemmP p) {  // 3 waves / SIMD: 3 workgroups per CU (LDS 48 KB)
+template <int BM, int BN, int LAYOUT, int EPI, bool FAST, bool BGATHER>
+__device__ __forceinline__ void gemm_x6_body(const GemmP& p, int vblock, int vgrid, uint8_t* smem) {
   constexpr bool AKC = (LAYOUT & 1) == 0, BKC = (LAYOUT & 2) == 0;
   constexpr int PA = BM * XBK, PB = BN * XBK, STG = 3 * (PA + PB);
   constexpr int TM = BM / 64, TN = BN / 64;
-  __shared__ __attribute__((aligned(16))) uint16_t S[2 * STG];
+  uint16_t* S = reinterpret_cast<uint16_t*>(smem);  // [2 * STG]
   const int mt = (p.M + BM - 1) / BM, nt = (p.N + BN - 1) / BN;
   int L;
   {
-    const int nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
+    const int nwg = vgrid, orig = vblock, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
     L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
   }
   const int tn_ = L % nt, tm_ = (L / nt) % mt, zz = L / (nt * mt);
@@ -1297,13 +1317,32 @@ __global__ __launch_bounds__(GTHREADS, 3) void gemm_x6_kernel(GemmP p) {  // 3 w
     }
   }
 }
+template <int BM, int BN, int LAYOUT, int EPI, bool FAST, bool BGATHER>
+struct X6Body {
+  static constexpr int LDS = 2 * 3 * (BM + BN) * XBK * (int)sizeof(uint16_t);
+  static __device__ __forceinline__ void run(const GemmP& p, int vblock, int vgrid, uint8_t* smem) {
+    gemm_x6_body<BM, BN, LAYOUT, EPI, FAST, BGATHER>(p, vblock, vgrid, smem);
+  }
+};
+// TAG: trace tag only (the weight-gradient shape, tn_shape_tag): each of the update's large weight gradients gets its own
+// symbol so a kernel trace / PMC pass keys its launches apart; the code is the same for every value
+template <int BM, int BN, int LAYOUT, int EPI, bool FAST, bool BGATHER, int TAG = 0>
+__global__ __launch_bounds__(GTHREADS, 3) void gemm_x6_kernel(GemmP p) {  // 3 waves / SIMD: 3 workgroups per CU (LDS 48 KB)
+  using Body = X6Body<BM, BN, LAYOUT, EPI, FAST, BGATHER>;
+  __shared__ __attribute__((aligned(16))) uint8_t S[Body::LDS];
+  Body::run(p, blockIdx.x, gridDim.x, S);
+}
 
+// every tile of the launch interior and every split's k range a whole number of slices: the FAST instantiation
+static bool x6_interior(const GemmP& p, int layout, int bm, int bn) {
+  const bool akc = (layout & 1) == 0, bkc = (layout & 2) == 0;
+  return p.M % bm == 0 && p.N % bn == 0 && p.K % XBK == 0 && p.kps % XBK == 0 && (!akc || p.avec == 4) &&
+         (!bkc || p.bvec == 4);
+}
 template <int BM, int BN>
 static int launch_x6_tile(const GemmP& p, int layout, int epi, int groups, hipStream_t st) {
   dim3 grid(((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * groups * p.splits);
-  const bool akc = (layout & 1) == 0, bkc = (layout & 2) == 0;
-  const bool interior = p.M % BM == 0 && p.N % BN == 0 && p.K % XBK == 0 && p.kps % XBK == 0 &&
-                        (!akc || p.avec == 4) && (!bkc || p.bvec == 4);
+  const bool interior = x6_interior(p, layout, BM, BN);
   const bool bg = p.b_rows != nullptr;
   if (layout == GEMM_TN) {  // (EPI_PARTIAL: try_x6 passes nothing else)
     auto tn = [&](auto F, auto G, auto T) {
@@ -1342,48 +1381,53 @@ static bool x6_enabled() {
 }
 
 static int try_x6d(const GemmP& p, int layout, int epi, int groups, int bm, int bn, hipStream_t st);
+static bool x6d_fits(const GemmP& p, int layout, int bm, int bn);
 
-// returns 1 when the product was launched on the x6 kernel (0: not eligible, <0: error)
-static int try_x6(const GemmP& p, int layout, int epi, int groups, hipStream_t st) {
-  if (!x6_enabled()) return 0;
+// the tile of gemm_x6_kernel for a product it takes (false: not eligible)
+static bool x6_tile(const GemmP& p, int layout, int epi, int groups, int& bm, int& bn) {
+  if (!x6_enabled()) return false;
   // (LRL_X6_MIN: development override of the smallest output side x6 takes — 16 by default)
   static const int min_side = getenv("LRL_X6_MIN") ? atoi(getenv("LRL_X6_MIN")) : 16;
-  if (p.N < min_side || (layout == GEMM_TN && p.M < min_side)) return 0;
+  if (p.N < min_side || (layout == GEMM_TN && p.M < min_side)) return false;
   // r-contiguous operands (A of TN, B of NN / TN) and the epilogue use 32-bit element offsets from the group base
   // (k * ld + row, row * ldc + col): keep every identity-indexed offset below 2^31 (gathered rows are 64-bit)
   const int64_t lim = int64_t(1) << 31;
-  if ((layout & 1) && (int64_t)p.K * p.lda >= lim) return 0;
-  if ((layout & 2) && p.b_rows == nullptr && (int64_t)p.K * p.ldb >= lim) return 0;
-  if ((int64_t)p.M * p.ldc >= lim || (epi_aux(epi) && (int64_t)p.M * p.ld_aux >= lim)) return 0;
-  int rc;
+  if ((layout & 1) && (int64_t)p.K * p.lda >= lim) return false;
+  if ((layout & 2) && p.b_rows == nullptr && (int64_t)p.K * p.ldb >= lim) return false;
+  if ((int64_t)p.M * p.ldc >= lim || (epi_aux(epi) && (int64_t)p.M * p.ld_aux >= lim)) return false;
   if (layout == GEMM_TN) {
     // (both operands r-contiguous: dword loads, any alignment)
-    if (epi != EPI_PARTIAL || p.M < 16 || p.N < 16 || p.kps % XBK) return 0;
-    const bool m64 = p.M <= 64, n64 = p.N <= 64;
-    if (m64 && n64) rc = launch_x6_tile<64, 64>(p, layout, epi, groups, st);
-    else if (m64) rc = launch_x6_tile<64, 128>(p, layout, epi, groups, st);
-    else if (n64) rc = launch_x6_tile<128, 64>(p, layout, epi, groups, st);
-    else rc = launch_x6_tile<128, 128>(p, layout, epi, groups, st);
-  } else {
-    if (p.splits != 1 || p.N < 16 || p.M < 64 || epi == EPI_PARTIAL) return 0;
-    // measured (scripts/gemm_bench.py): one or two 16-k slices do not pay the split / staging set-up, and the
-    // thin kernel (B in registers) stays faster for <= 32-wide outputs over k = 512 / 1024
-    if (p.K < 32) return 0;
-    if (p.N <= 32 && p.K % 128 == 0 && (p.K / 128 == 4 || p.K / 128 == 8) && p.avec == 4 && p.M >= 256) return 0;
-    // (LRL_X6_SMALL_WG: development override — below this many 64 x 128 workgroups the product takes 64 x 64 tiles)
-    static const int small_wg = getenv("LRL_X6_SMALL_WG") ? atoi(getenv("LRL_X6_SMALL_WG")) : 1024;
-    int bn = p.N > 64 ? 128 : 64;
-    if (bn == 128 && (int64_t)((p.M + 63) / 64) * ((p.N + 127) / 128) * groups < small_wg) bn = 64;
-    // 128-row tiles when they still give two workgroups per CU, 64 otherwise
-    const int64_t wg128 = (int64_t)((p.M + 127) / 128) * ((p.N + bn - 1) / bn) * groups;
-    const int bm = wg128 >= 512 ? 128 : 64;
-    // the same tile on the LDS-DMA kernel where the tiles are interior
-    if (int dr = try_x6d(p, layout, epi, groups, bm, bn, st)) return dr;
-    if (bm == 128 && bn == 128) rc = launch_x6_tile<128, 128>(p, layout, epi, groups, st);
-    else if (bm == 128) rc = launch_x6_tile<128, 64>(p, layout, epi, groups, st);
-    else if (bn == 128) rc = launch_x6_tile<64, 128>(p, layout, epi, groups, st);
-    else rc = launch_x6_tile<64, 64>(p, layout, epi, groups, st);
+    if (epi != EPI_PARTIAL || p.M < 16 || p.N < 16 || p.kps % XBK) return false;
+    bm = p.M <= 64 ? 64 : 128;
+    bn = p.N <= 64 ? 64 : 128;
+    return true;
   }
+  if (p.splits != 1 || p.N < 16 || p.M < 64 || epi == EPI_PARTIAL) return false;
+  // measured (scripts/gemm_bench.py): one or two 16-k slices do not pay the split / staging set-up, and the
+  // thin kernel (B in registers) stays faster for <= 32-wide outputs over k = 512 / 1024
+  if (p.K < 32) return false;
+  if (p.N <= 32 && p.K % 128 == 0 && (p.K / 128 == 4 || p.K / 128 == 8) && p.avec == 4 && p.M >= 256) return false;
+  // (LRL_X6_SMALL_WG: development override — below this many 64 x 128 workgroups the product takes 64 x 64 tiles)
+  static const int small_wg = getenv("LRL_X6_SMALL_WG") ? atoi(getenv("LRL_X6_SMALL_WG")) : 1024;
+  bn = p.N > 64 ? 128 : 64;
+  if (bn == 128 && (int64_t)((p.M + 63) / 64) * ((p.N + 127) / 128) * groups < small_wg) bn = 64;
+  // 128-row tiles when they still give two workgroups per CU, 64 otherwise
+  const int64_t wg128 = (int64_t)((p.M + 127) / 128) * ((p.N + bn - 1) / bn) * groups;
+  bm = wg128 >= 512 ? 128 : 64;
+  return true;
+}
+
+// returns 1 when the product was launched on the x6 kernel (0: not eligible, <0: error)
+static int try_x6(const GemmP& p, int layout, int epi, int groups, hipStream_t st) {
+  int bm, bn;
+  if (!x6_tile(p, layout, epi, groups, bm, bn)) return 0;
+  // the same tile on the LDS-DMA kernel where the tiles are interior (NT / NN)
+  if (int dr = try_x6d(p, layout, epi, groups, bm, bn, st)) return dr;
+  int rc;
+  if (bm == 128 && bn == 128) rc = launch_x6_tile<128, 128>(p, layout, epi, groups, st);
+  else if (bm == 128) rc = launch_x6_tile<128, 64>(p, layout, epi, groups, st);
+  else if (bn == 128) rc = launch_x6_tile<64, 128>(p, layout, epi, groups, st);
+  else rc = launch_x6_tile<64, 64>(p, layout, epi, groups, st);
   return rc ? rc : 1;
 }
 
@@ -1540,19 +1584,18 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6p_kernel(GemmP p) {
 // 4 waves of 2 x 2 MFMA tiles, x6_mma steps over gemm_x6_kernel's k order, and the bias gradient partial summed in its
 // (row, k-half) order.
 constexpr int X6T_MAX_GATHER_KPS = 1024;  // gathered-B splits of at most this many rows (the row list in LDS)
-template <int BN, int TAG, bool BGATHER>
-__global__ __launch_bounds__(GTHREADS, 2) void gemm_x6t_kernel(GemmP p) {
+template <int BN, bool BGATHER>
+__device__ __forceinline__ void gemm_x6t_body(const GemmP& p, int vblock, int vgrid, uint8_t* S) {
   constexpr int BM = 128, NST = 3, TM = 2, TN = BN / 64;
   constexpr int IMG = 16 * 128 * 4, STB = IMG + 16 * BN * 4;  // bytes: A image [16][128], then B image [16][BN]
   constexpr int NAP = IMG / 1024, NBP = BN / 16;              // DMA pieces (1 KiB wave-instructions) per stage
   constexpr int NPW = (NAP + NBP) / 4;                        // per wave: 4 (BN 128) or 3 (BN 64)
   constexpr int KPP = 256 / BN;                               // k-rows per B piece
-  constexpr int XROWS = BGATHER ? X6T_MAX_GATHER_KPS : 0;  // gathered B: the split's row list (int32) after the ring
-  __shared__ __attribute__((aligned(16))) uint8_t S[NST * STB + 4 * XROWS];
+  // S: [NST * STB] ring, then (gathered B) the split's row list, X6T_MAX_GATHER_KPS int32 (X6tBody::LDS)
   const int mt = p.M / BM, nt = (p.N + BN - 1) / BN;  // (ragged n: see try_x6t)
   int L;
   {
-    const int nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
+    const int nwg = vgrid, orig = vblock, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
     L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
   }
   const int tn_ = L % nt, tm_ = (L / nt) % mt, zz = L / (nt * mt);
@@ -1696,6 +1739,20 @@ __global__ __launch_bounds__(GTHREADS, 2) void gemm_x6t_kernel(GemmP p) {
       p.bias_part[((int64_t)sp * p.groups + g) * p.M + m0 + threadIdx.x] = s;
     }
   }
+}
+template <int BN, bool BGATHER>
+struct X6tBody {
+  static constexpr int LDS = 3 * (16 * 128 * 4 + 16 * BN * 4) + (BGATHER ? 4 * X6T_MAX_GATHER_KPS : 0);
+  static __device__ __forceinline__ void run(const GemmP& p, int vblock, int vgrid, uint8_t* smem) {
+    gemm_x6t_body<BN, BGATHER>(p, vblock, vgrid, smem);
+  }
+};
+// TAG: trace tag only (tn_shape_tag)
+template <int BN, int TAG, bool BGATHER>
+__global__ __launch_bounds__(GTHREADS, 2) void gemm_x6t_kernel(GemmP p) {
+  using Body = X6tBody<BN, BGATHER>;
+  __shared__ __attribute__((aligned(16))) uint8_t S[Body::LDS];
+  Body::run(p, blockIdx.x, gridDim.x, S);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1880,11 +1937,14 @@ static int x6d_mode() {
 static bool x6d_enabled() { return x6d_mode() != 0; }
 
 // returns 1 when launched on the x6d kernel (0: not eligible, <0: error); bm / bn: the tile gemm_x6_kernel would take
+static bool x6d_fits(const GemmP& p, int layout, int bm, int bn) {
+  if (!x6d_enabled() || (layout != GEMM_NT && layout != GEMM_NN) || p.splits != 1) return false;
+  if (layout == GEMM_NT && x6d_mode() != 2) return false;
+  if (p.M % bm || p.N % bn || p.K % 16 || p.K < 32 || p.avec != 4 || p.bvec != 4) return false;
+  return !(layout == GEMM_NN && p.b_rows);
+}
 static int try_x6d(const GemmP& p, int layout, int epi, int groups, int bm, int bn, hipStream_t st) {
-  if (!x6d_enabled() || (layout != GEMM_NT && layout != GEMM_NN) || p.splits != 1) return 0;
-  if (layout == GEMM_NT && x6d_mode() != 2) return 0;
-  if (p.M % bm || p.N % bn || p.K % 16 || p.K < 32 || p.avec != 4 || p.bvec != 4) return 0;
-  if (layout == GEMM_NN && p.b_rows) return 0;
+  if (!x6d_fits(p, layout, bm, bn)) return 0;
   const int rc = with_int(layout, BatchMajor{}, [&](auto L) {
     constexpr int LAYOUT = decltype(L)::value;
     if (bm == 128 && bn == 128) return launch_x6d_l<128, 128, LAYOUT>(p, epi, groups, st);
@@ -1904,13 +1964,20 @@ static bool x6t_enabled() {
 
 // returns 1 when launched on the x6t kernel (0: not eligible, <0: error).  n may be ragged when B's row pitch covers
 // the last tile (the DMA reads whole 128-wide tiles); a gathered B keeps its split's row list in LDS
-static int try_x6t(const GemmP& p, int layout, int epi, int groups, hipStream_t st) {
+// the n tile (64 / 128) of the x6t kernel for a product it takes, 0 for any other product
+static int x6t_tile(const GemmP& p, int layout, int epi) {
   if (!x6t_enabled() || layout != GEMM_TN || epi != EPI_PARTIAL) return 0;
   const int bn = p.N <= 64 ? 64 : 128, nt = (p.N + bn - 1) / bn;
   if (p.M % 128 || p.K % 16 || p.kps % 16 || p.kps < 16 || p.avec != 4 || p.bvec != 4) return 0;
   if ((int64_t)nt * bn > p.ldb) return 0;
   if (p.b_rows && p.kps > X6T_MAX_GATHER_KPS) return 0;
   if ((int64_t)(p.splits - 1) * p.kps >= p.K) return 0;  // (every split has a non-empty range)
+  return bn;
+}
+static int try_x6t(const GemmP& p, int layout, int epi, int groups, hipStream_t st) {
+  const int bn = x6t_tile(p, layout, epi);
+  if (!bn) return 0;
+  const int nt = (p.N + bn - 1) / bn;
   dim3 grid((unsigned)((p.M / 128) * nt * groups * p.splits));  // (stores stop at p.N)
   note_path(FAM_X6T, 128, bn);
   if (bn == 64) {
@@ -2071,8 +2138,8 @@ int gemm_pick_splits(int M, int N, int K, int groups) {
 
 int gemm_last_path() { return g_last_path; }
 
-int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) {
-  GemmP p = p0;
+// gemm_launch's view of a product: the shape / pair checks, the split and the staging widths filled in
+static int gemm_prepare(GemmP& p, int layout, int epi, int groups) {
   if (p.M <= 0 || p.N <= 0 || p.K < 0 || groups <= 0) return LRL_E_INVALID;
   // a pair outside the table (Offered) is refused here, in front of every family, whatever the shape and the switches;
   // so is the tanh backward without its aux operand
@@ -2083,28 +2150,57 @@ int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) 
   p.kps = (p.kps + GBK - 1) / GBK * GBK;
   p.avec = vec_width(p.A, p.lda, p.ga);
   p.bvec = vec_width(p.B, p.ldb, p.gb);
-  int bm, bn;
-  pick_tile(p.M, p.N, layout == GEMM_TN, bm, bn);
   p.groups = groups;
-  dim3 grid(((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * groups * p.splits);
-  hipStream_t st = static_cast<hipStream_t>(stream);
   static const bool trace = getenv("LRL_GEMM_TRACE") != nullptr;  // shape log for profiling runs
   if (trace)
     fprintf(stderr, "gemm layout=%d epi=%d M=%d N=%d K=%d groups=%d splits=%d avec=%d bvec=%d arows=%d brows=%d\n",
             layout, epi, p.M, p.N, p.K, groups, p.splits, p.avec, p.bvec, p.a_rows != nullptr, p.b_rows != nullptr);
+  return 0;
+}
+#ifndef LRL_GLDS_BK32
+#define LRL_GLDS_BK32 1
+#endif
+#ifndef LRL_GLDS_TN
+#define LRL_GLDS_TN 1
+#endif
+// LDS-DMA path: batch-major product, every tile interior, float4-aligned operands, single split
+static bool glds_fits(const GemmP& p, int layout, int epi) {
+  return layout != GEMM_TN && p.splits == 1 && p.M % 64 == 0 && p.N % 64 == 0 && p.K % 16 == 0 && p.K >= 32 &&
+         p.avec == 4 && p.bvec == 4 && epi != EPI_PARTIAL && (layout == GEMM_NT || layout == GEMM_NN);
+}
+// LDS-DMA weight gradient: 128-row m tiles, 128-wide n tiles whose reads stay inside the row pitch,
+// whole 16-row slices in every split, float4-aligned operands.  Returns the n tile, 0 when the product does not fit
+static int glds_tn_tile(const GemmP& p, int layout, int epi) {
+  if (LRL_GLDS_TN && layout == GEMM_TN && epi == EPI_PARTIAL && p.M % 128 == 0 && p.K % 16 == 0 &&
+      p.kps % 16 == 0 && p.avec == 4 && p.bvec == 4 && p.kps <= 8192) {
+    if (p.N <= 64 && p.ldb >= 64) return 64;
+    if ((int64_t)((p.N + 127) / 128) * 128 <= p.ldb) return 128;
+  }
+  return 0;
+}
+// thin output (N <= 32): B staged whole in LDS, k split over the workgroup's waves
+static bool thin_fits(const GemmP& p, int layout, int epi) {
+  const int kb128 = p.K / 128;
+  return layout != GEMM_TN && p.splits == 1 && p.N <= 32 && p.K % 128 == 0 && p.avec == 4 && p.M >= 256 &&
+         (kb128 == 4 || kb128 == 8) &&  // (shorter k: the register-staged 128 x 32 tile is as fast)
+         (epi == EPI_STORE || epi_bias(epi));
+}
+
+int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) {
+  GemmP p = p0;
+  if (int rc = gemm_prepare(p, layout, epi, groups)) return rc;
+  int bm, bn;
+  pick_tile(p.M, p.N, layout == GEMM_TN, bm, bn);
+  dim3 grid(((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * groups * p.splits);
+  hipStream_t st = static_cast<hipStream_t>(stream);
   // weight products with a pre-split B: the LDS-DMA x6p kernel
   g_last_path = 0;
   if (int xr = try_x6p(p, layout, epi, groups, st)) return xr > 0 ? 0 : xr;
   if (int xr = try_x6t(p, layout, epi, groups, st)) return xr > 0 ? 0 : xr;
   // fp32 on the bf16 MFMA (exact split, fp32-class error) wherever the tile shapes fit
   if (int xr = try_x6(p, layout, epi, groups, st)) return xr > 0 ? 0 : xr;
-  // LDS-DMA path: batch-major product, every tile interior, float4-aligned operands, single split
-  if (layout != GEMM_TN && p.splits == 1 && p.M % 64 == 0 && p.N % 64 == 0 && p.K % 16 == 0 && p.K >= 32 &&
-      p.avec == 4 && p.bvec == 4 && epi != EPI_PARTIAL && (layout == GEMM_NT || layout == GEMM_NN)) {
+  if (glds_fits(p, layout, epi)) {
     dim3 g1((p.M / 64) * (p.N / 64) * groups);
-#ifndef LRL_GLDS_BK32
-#define LRL_GLDS_BK32 1
-#endif
     const bool bk32 = LRL_GLDS_BK32 && p.K % 32 == 0 && p.K >= 64;
     const int rc = with_pair(layout, epi, BatchMajor{}, [&](auto L, auto E) {
       if (bk32) hipLaunchKernelGGL((gemm_glds_kernel<L(), E(), 32>), g1, dim3(GTHREADS), 0, st, p);
@@ -2115,22 +2211,10 @@ int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) 
     note_path(bk32 ? FAM_GLDS32 : FAM_GLDS, 64, 64);
     return hipGetLastError() == hipSuccess ? 0 : LRL_E_HIP;
   }
-  // LDS-DMA weight gradient: 128-row m tiles, 128-wide n tiles whose reads stay inside the row pitch,
-  // whole 16-row slices in every split, float4-aligned operands
-#ifndef LRL_GLDS_TN
-#define LRL_GLDS_TN 1
-#endif
-  if (LRL_GLDS_TN && layout == GEMM_TN && epi == EPI_PARTIAL && p.M % 128 == 0 && p.K % 16 == 0 &&
-      p.kps % 16 == 0 && p.avec == 4 && p.bvec == 4 && p.kps <= 8192) {
-    if (p.N <= 64 && p.ldb >= 64) return launch_glds_tn<64>(p, groups, st);
-    if ((int64_t)((p.N + 127) / 128) * 128 <= p.ldb) return launch_glds_tn<128>(p, groups, st);
-  }
-  // thin output (N <= 32): B staged whole in LDS, k split over the workgroup's waves
-  const int kb128 = p.K / 128;
-  if (layout != GEMM_TN && p.splits == 1 && p.N <= 32 && p.K % 128 == 0 && p.avec == 4 && p.M >= 256 &&
-      (kb128 == 4 || kb128 == 8) &&  // (shorter k: the register-staged 128 x 32 tile is as fast)
-      (epi == EPI_STORE || epi_bias(epi))) {
-    // (the condition above leaves NN its store epilogue only: the thin kernels have no aux operand)
+  if (const int tbn = glds_tn_tile(p, layout, epi))
+    return tbn == 64 ? launch_glds_tn<64>(p, groups, st) : launch_glds_tn<128>(p, groups, st);
+  if (thin_fits(p, layout, epi)) {
+    // (thin_fits leaves NN its store epilogue only: the thin kernels have no aux operand)
     const int trc = with_pair(layout, epi, BatchMajor{}, [&](auto L, auto E) {
       if constexpr (epi_aux(decltype(E)::value)) return LRL_E_INVALID;
       else return launch_thin<L(), E()>(p, groups, st);
@@ -2148,6 +2232,142 @@ int gemm_launch(const GemmP& p0, int layout, int epi, int groups, void* stream) 
   if (rc) return rc;
   note_path(FAM_STAGED, bm, bn);
   return hipGetLastError() == hipSuccess ? 0 : LRL_E_HIP;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Multi-problem launch: up to MAX_MULTI_JOBS products that do not depend on each other in one kernel, whose grid is the
+// concatenation of the grids gemm_launch would give each of them (job 0's workgroups first).  A workgroup finds its job
+// from blockIdx.x (a workgroup-uniform branch: the bodies' raw barriers and counted vmcnt waits see no divergence, and
+// each workgroup runs one body to its end, so no LDS-DMA is in flight when another could start), and runs that job's
+// kernel body — the same device function, tile and split as its own launch — on (vblock, vgrid) = its place in the job's
+// grid and the job's grid size, in one LDS block of the largest member's size.  So every output is bit-identical to the
+// separate launches.  The small products of the update's backward tail ride this way in front of a large weight
+// gradient's workgroups and finish in its shadow, instead of on a second stream (lrl_ppo.hip).
+// The bodies a job can map to (the dispatcher's decision for it, gemm_launch's order of families):
+enum MultiBody : int {
+  MB_NONE = 0,
+  MB_X6T128,   // x6t, 128-wide n tile, B not gathered
+  MB_X6T64,    // x6t, 64-wide n tile, B not gathered
+  MB_X6_TN_64x128_G,    // x6 <64, 128, TN, PARTIAL, guarded>
+  MB_X6_TN_128x64_GG,   // x6 <128, 64, TN, PARTIAL, guarded, gathered B>
+  MB_X6_NN_128x64_F,    // x6 <128, 64, NN, DELU, fast>
+  MB_X6_NN_64x64_F,     // x6 <64, 64, NN, DELU, fast> (the same product at fewer rows)
+  MB_STAGED_NN_64x64,   // gemm_kernel <64, 64, NN, DELU>
+};
+template <int ID> struct MultiBodyOf;
+template <> struct MultiBodyOf<MB_X6T128> { using type = X6tBody<128, false>; };
+template <> struct MultiBodyOf<MB_X6T64> { using type = X6tBody<64, false>; };
+template <> struct MultiBodyOf<MB_X6_TN_64x128_G> { using type = X6Body<64, 128, GEMM_TN, EPI_PARTIAL, false, false>; };
+template <> struct MultiBodyOf<MB_X6_TN_128x64_GG> { using type = X6Body<128, 64, GEMM_TN, EPI_PARTIAL, false, true>; };
+template <> struct MultiBodyOf<MB_X6_NN_128x64_F> { using type = X6Body<128, 64, GEMM_NN, EPI_DELU, true, false>; };
+template <> struct MultiBodyOf<MB_X6_NN_64x64_F> { using type = X6Body<64, 64, GEMM_NN, EPI_DELU, true, false>; };
+template <> struct MultiBodyOf<MB_STAGED_NN_64x64> { using type = StagedBody<64, 64, GEMM_NN, EPI_DELU>; };
+
+// body, grid size and path report of a prepared product; MB_NONE for a product no multi kernel carries
+struct MultiPick {
+  int body, grid, path;
+};
+static MultiPick multi_pick(const GemmP& p, int layout, int epi, int groups) {
+  const MultiPick none{MB_NONE, 0, 0};
+  if (p.bpl) return none;  // (a pre-split B goes to x6p)
+  if (const int bn = x6t_tile(p, layout, epi)) {
+    if (p.b_rows) return none;
+    const int grid = (p.M / 128) * ((p.N + bn - 1) / bn) * groups * p.splits;
+    return {bn == 128 ? MB_X6T128 : MB_X6T64, grid, gemm_path_id(FAM_X6T, 128, bn, false)};
+  }
+  int bm, bn;
+  if (x6_tile(p, layout, epi, groups, bm, bn)) {
+    if (x6d_fits(p, layout, bm, bn)) return none;
+    const bool interior = x6_interior(p, layout, bm, bn), bg = p.b_rows != nullptr;
+    const int grid = ((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * groups * p.splits;
+    const int path = gemm_path_id(FAM_X6, bm, bn, interior);
+    if (layout == GEMM_TN && bm == 64 && bn == 128 && !interior && !bg) return {MB_X6_TN_64x128_G, grid, path};
+    if (layout == GEMM_TN && bm == 128 && bn == 64 && !interior && bg) return {MB_X6_TN_128x64_GG, grid, path};
+    if (layout == GEMM_NN && epi == EPI_DELU && bn == 64 && interior)
+      return {bm == 128 ? MB_X6_NN_128x64_F : MB_X6_NN_64x64_F, grid, path};
+    return none;
+  }
+  if (glds_fits(p, layout, epi) || glds_tn_tile(p, layout, epi) || thin_fits(p, layout, epi)) return none;
+  pick_tile(p.M, p.N, layout == GEMM_TN, bm, bn);
+  if (layout == GEMM_NN && epi == EPI_DELU && bm == 64 && bn == 64) {
+    const int grid = ((p.M + 63) / 64) * ((p.N + 63) / 64) * groups * p.splits;
+    return {MB_STAGED_NN_64x64, grid, gemm_path_id(FAM_STAGED, 64, 64, false)};
+  }
+  return none;
+}
+
+template <int NJ>
+struct MultiP {
+  GemmP p[NJ];
+  int end[NJ];  // one past job i's last workgroup in the concatenated grid
+};
+template <int I, int NJ, class Body, class... Rest>
+__device__ __forceinline__ void multi_run(const MultiP<NJ>& J, int b, uint8_t* smem) {
+  const int beg = I ? J.end[I ? I - 1 : 0] : 0;
+  if constexpr (sizeof...(Rest) == 0) {
+    Body::run(J.p[I], b - beg, J.end[I] - beg, smem);
+  } else {
+    if (b < J.end[I]) Body::run(J.p[I], b - beg, J.end[I] - beg, smem);
+    else multi_run<I + 1, NJ, Rest...>(J, b, smem);
+  }
+}
+template <class... Body>
+__global__ __launch_bounds__(GTHREADS, 2) void gemm_multi_kernel(MultiP<(int)sizeof...(Body)> J) {
+  __shared__ __attribute__((aligned(16))) uint8_t S[std::max({Body::LDS...})];  // the largest member's, not the sum
+  multi_run<0, (int)sizeof...(Body), Body...>(J, (int)blockIdx.x, S);
+}
+
+// The combinations on offer, in grid order (riders first, the host — the large weight gradient — last); they cover
+// the backward tail of the preset networks (lrl_ppo_forward_backward):
+//   A  dWe3, dhe2, dW3:  x6 <64,128,TN,guarded> + staged <64,64,NN,DELU> + x6t BN128
+//   B  dWe2, dhe1, host: x6t BN128 + x6 <128 | 64, 64, NN, DELU, fast> + x6t (either n tile)
+//   C  dWe1, host:       x6 <128,64,TN,guarded,gathered B> + x6t (either n tile)
+// and B's two riders without a host (the update launches its timed product alone: lrl_ppo_timing).
+template <int... IDS>
+struct MultiCombo {};
+using MultiCombos = std::tuple<MultiCombo<MB_X6_TN_64x128_G, MB_STAGED_NN_64x64, MB_X6T128>,
+                               MultiCombo<MB_X6T128, MB_X6_NN_128x64_F, MB_X6T128>,
+                               MultiCombo<MB_X6T128, MB_X6_NN_128x64_F, MB_X6T64>,
+                               MultiCombo<MB_X6T128, MB_X6_NN_64x64_F, MB_X6T128>,
+                               MultiCombo<MB_X6T128, MB_X6_NN_64x64_F, MB_X6T64>,
+                               MultiCombo<MB_X6T128, MB_X6_NN_128x64_F>, MultiCombo<MB_X6T128, MB_X6_NN_64x64_F>,
+                               MultiCombo<MB_X6_TN_128x64_GG, MB_X6T128>,
+                               MultiCombo<MB_X6_TN_128x64_GG, MB_X6T64>>;
+
+template <int... IDS>
+static bool multi_try(MultiCombo<IDS...>, const GemmP* p, const MultiPick* pick, int n, hipStream_t st) {
+  constexpr int NJ = (int)sizeof...(IDS);
+  constexpr int ids[NJ] = {IDS...};
+  if (n != NJ) return false;
+  for (int i = 0; i < NJ; ++i)
+    if (pick[i].body != ids[i]) return false;
+  MultiP<NJ> J;
+  int total = 0;
+  for (int i = 0; i < NJ; ++i) {
+    J.p[i] = p[i];
+    total += pick[i].grid;
+    J.end[i] = total;
+  }
+  hipLaunchKernelGGL((gemm_multi_kernel<typename MultiBodyOf<IDS>::type...>), dim3((unsigned)total), dim3(GTHREADS), 0,
+                     st, J);
+  return true;
+}
+
+int gemm_launch_multi(const GemmJob* jobs, int n, void* stream) {
+  if (!jobs || n < 2 || n > MAX_MULTI_JOBS) return 0;
+  GemmP p[MAX_MULTI_JOBS];
+  MultiPick pick[MAX_MULTI_JOBS];
+  for (int i = 0; i < n; ++i) {
+    p[i] = jobs[i].p;
+    if (int rc = gemm_prepare(p[i], jobs[i].layout, jobs[i].epi, jobs[i].groups)) return rc;
+    pick[i] = multi_pick(p[i], jobs[i].layout, jobs[i].epi, jobs[i].groups);
+    if (pick[i].body == MB_NONE || pick[i].grid <= 0) return 0;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool hit = std::apply([&](auto... c) { return (multi_try(c, p, pick, n, st) || ...); }, MultiCombos{});
+  if (!hit) return 0;
+  g_last_path = pick[n - 1].path;
+  return hipGetLastError() == hipSuccess ? 1 : LRL_E_HIP;
 }
 
 }  // namespace lrl

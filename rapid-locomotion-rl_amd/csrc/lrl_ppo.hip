@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <mutex>
 #include <vector>
 
@@ -1263,6 +1264,15 @@ struct G {
     if (pl) gemm_use_planes(p, *pl);
     pl = nullptr;
   }
+  // collect, don't launch: with `jobs` set, every product is appended there (as gemm_launch would receive it) for the
+  // caller to launch, alone or as a multi-problem launch (launch_jobs); everything else the helpers do stays the same
+  GemmJob* jobs = nullptr;
+  int njobs = 0, max_jobs = 0;
+  void launch(const GemmP& p, int layout, int epi, int groups) {
+    if (!jobs) rc = gemm_launch(p, layout, epi, groups, st);
+    else if (njobs < max_jobs) jobs[njobs++] = GemmJob{p, layout, epi, groups};
+    else rc = LRL_E_INVALID;
+  }
   void nt(const float* A, int64_t lda, const int64_t* rows, const float* W, int64_t ldw, float* C, int64_t ldc,
           const float* bias, int M, int N, int K, bool elu, int groups = 1, int64_t ga = 0, int64_t gw = 0,
           int64_t gc = 0, int64_t gbias = 0) {
@@ -1272,7 +1282,7 @@ struct G {
     p.M = M; p.N = N; p.K = K; p.splits = 1;
     p.ga = ga; p.gb = gw; p.gc = gc; p.gbias = gbias;
     take_planes(p);
-    rc = gemm_launch(p, GEMM_NT, elu ? (tanh_act ? EPI_BIAS_TANH : EPI_BIAS_ELU) : EPI_BIAS, groups, st);
+    launch(p, GEMM_NT, elu ? (tanh_act ? EPI_BIAS_TANH : EPI_BIAS_ELU) : EPI_BIAS, groups);
   }
   // dX = dY W (* elu'(aux) if aux)
   void nn(const float* dY, int64_t ldy, const float* W, int64_t ldw, float* dX, int64_t ldx, const float* aux,
@@ -1284,7 +1294,7 @@ struct G {
     p.M = M; p.N = N; p.K = K; p.splits = 1;
     p.ga = gy; p.gb = gw; p.gc = gx; p.gaux = gaux;
     take_planes(p);
-    rc = gemm_launch(p, GEMM_NN, aux ? (tanh_act ? EPI_DTANH : EPI_DELU) : EPI_STORE, groups, st);
+    launch(p, GEMM_NN, aux ? (tanh_act ? EPI_DTANH : EPI_DELU) : EPI_STORE, groups);
   }
   // partial dW[o][i] = sum_b dY[b][o] X[rows(b)][i]; returns the segments (weights then biases)
   void tn(const float* dY, int64_t ldy, const float* X, int64_t ldx, const int64_t* rows, int M, int N, int K,
@@ -1299,7 +1309,7 @@ struct G {
     p.part_stride = (int64_t)groups * M * N;
     p.C = part;
     p.bias_part = part + (int64_t)splits * groups * M * N;
-    rc = gemm_launch(p, GEMM_TN, EPI_PARTIAL, groups, st);
+    launch(p, GEMM_TN, EPI_PARTIAL, groups);
     if (rc) return;
     if (L.n + 2 > MAX_SEGS) { rc = LRL_E_INVALID; return; }
     L.s[L.n++] = Seg{part, dw, (int64_t)groups * M * N, (int64_t)groups * M * N, splits, 1.f};
@@ -1309,10 +1319,40 @@ struct G {
   }
 };
 
-// The env-factor encoder's backward chain (five small products at the minibatch's rows, latency-bound) runs on a
+// Launch the collected jobs all[idx[0 .. n)] in that order: as one multi-problem launch where the set is one that
+// gemm_launch_multi offers, one by one otherwise (other widths, the fp32 paths of lrl_debug_gemm_paths, LRL_GEMM_X6=0).
+static int launch_jobs(const GemmJob* all, std::initializer_list<int> idx, hipStream_t st) {
+  GemmJob js[MAX_MULTI_JOBS];
+  int n = 0;
+  for (int i : idx) {
+    if (n == MAX_MULTI_JOBS) return LRL_E_INVALID;
+    js[n++] = all[i];
+  }
+  if (n > 1) {
+    const int r = gemm_launch_multi(js, n, st);
+    if (r) return r < 0 ? r : 0;
+  }
+  for (int i = 0; i < n; ++i)
+    if (int rc = gemm_launch(js[i].p, js[i].layout, js[i].epi, js[i].groups, st)) return rc;
+  return 0;
+}
+
+// How the backward tail of lrl_ppo_forward_backward packs its eight products, LRL_PPO_BWD_MULTI read at every call (a
+// test flips it in one process): 1 (default) = three multi-problem launches on the caller's stream, the encoder's
+// products riding in front of the weight gradients' workgroups — {dWe3, dhe2 | dW3}, {dWe2, dhe1 | dW1}, {dWe1 | dW2};
+// 2 and 3 = the same riders on other hosts (measurement switches: dW3, dW2, dW1 and dW2, dW1, dW3); 0 = eight
+// launches, the encoder's chain forked to the library's second stream (below).  Every setting gives the same bits.
+static int bwd_multi_mode() {
+  const char* e = getenv("LRL_PPO_BWD_MULTI");
+  return e && e[0] >= '0' && e[0] <= '3' ? e[0] - '0' : 1;
+}
+
+// The fallback path (LRL_PPO_BWD_MULTI=0; the default packs the chain into the weight-gradient launches instead): the
+// env-factor encoder's backward chain (five small products at the minibatch's rows, latency-bound) runs on a
 // second stream of the library's own, beside the actor / critic weight gradients of the same minibatch (they share no
 // buffer: the chain reads dlat / he1 / he2 / priv and the weights, writes dhe1 / dhe2 and its own partial slices).
-// One stream and two events per device, created on first use.  LRL_PPO_FORK=0 keeps everything on the caller's stream.
+// One stream and two events per device, created on first use.  LRL_PPO_FORK=0 (read at every call) keeps everything on
+// the caller's stream.
 struct Fork {
   hipStream_t st = nullptr;
   hipEvent_t go = nullptr, done = nullptr;
@@ -1322,11 +1362,8 @@ struct Fork {
 // device share its fork: the stream is in order, so a later `done` record still covers an earlier caller's chain (at
 // worst a caller waits for more work than its own).
 static Fork* fork_for_device(hipStream_t caller) {
-  static const bool on = [] {
-    const char* e = getenv("LRL_PPO_FORK");
-    return !(e && e[0] == '0');
-  }();
-  if (!on) return nullptr;
+  const char* e = getenv("LRL_PPO_FORK");
+  if (e && e[0] == '0') return nullptr;
   static Fork forks[64];
   static std::mutex mu;
   int dev = 0;
@@ -1789,13 +1826,52 @@ extern "C" int32_t lrl_ppo_forward_backward(const lrl_ppo_net* net, const float*
     part += ((hb * pl + 63) / 64) * 64;
   }
   // ---- backward ----
-  // the data-gradient chain first (dH2, dH1, the latent gradient), then the encoder's chain forks to the library's
-  // second stream while the actor / critic weight gradients run here; the split-k reduction joins both
+  // the data-gradient chain first (dH2, dH1, the latent gradient), then the encoder's chain and the actor / critic
+  // weight gradients: packed into three multi-problem launches (bwd_multi_mode), or, as the fallback, the chain forked to
+  // the library's second stream while the weight gradients run here; the split-k reduction waits for all of them
   const int h0 = n.ac_h0, h1 = n.ac_h1, h2 = n.ac_h2;
   g.with(PJ(PL_W3T)).nn(P.dh3, 2 * h2, w + n.w3, h1, P.dh2, 2 * h1, P.h2, 2 * h1, B, h1, h2, 2, h2, (int64_t)h2 * h1, h1, h1);
   g.with(PJ(PL_W2T)).nn(P.dh2, 2 * h1, w + n.w2, h0, P.dh1, 2 * h0, P.h1, 2 * h0, B, h0, h1, 2, h1, (int64_t)h1 * h0, h0, h0);
   // d latent = dH1 [W1a; W1c][:, num_obs:]  (sum over actor and critic halves: one reduction of length 2*h0)
   g.nn(P.dh1, 2 * h0, w + n.w1 + n.num_obs, nx, P.dlat, LATS, nullptr, 0, B, n.latent, 2 * h0);
+  if (const int mode = bwd_multi_mode()) {
+    // the eight products are collected in the fallback path's order (so the partial area and the segment list are
+    // laid out exactly as there), then launched as three sets: the encoder's chain needs dlat -> dhe2 -> dhe1 in turn,
+    // the actor / critic weight gradients need none of them
+    enum { DWE3, DHE2, DWE2, DHE1, DWE1, DW3, DW2, DW1, NJOBS };
+    GemmJob jobs[NJOBS];
+    G gc{st, g.part_end};
+    gc.jobs = jobs;
+    gc.max_jobs = NJOBS;
+    gc.tn(P.dlat, LATS, P.he2, n.enc_h1, nullptr, n.latent, n.enc_h1, B, 1, 0, 0, part, grads + n.e3w, grads + n.e3b, L);
+    gc.nn(P.dlat, LATS, w + n.e3w, n.enc_h1, P.dhe2, n.enc_h1, P.he2, n.enc_h1, B, n.enc_h1, n.latent);
+    gc.tn(P.dhe2, n.enc_h1, P.he1, n.enc_h0, nullptr, n.enc_h1, n.enc_h0, B, 1, 0, 0, part, grads + n.e2w, grads + n.e2b, L);
+    gc.with(PJ(PL_E2T)).nn(P.dhe2, n.enc_h1, w + n.e2w, n.enc_h0, P.dhe1, n.enc_h0, P.he1, n.enc_h0, B, n.enc_h0, n.enc_h1);
+    gc.tn(P.dhe1, n.enc_h0, bt->priv, n.num_priv, bt->rows, n.enc_h0, n.num_priv, B, 1, 0, 0, part, grads + n.e1w,
+          grads + n.e1b, L);
+    gc.tn(P.dh3, 2 * h2, P.h2, 2 * h1, nullptr, h2, h1, B, 2, h2, h1, part, grads + n.w3, grads + n.b3, L);
+    gc.tn(P.dh2, 2 * h1, P.h1, 2 * h0, nullptr, h1, h0, B, 2, h1, h0, part, grads + n.w2, grads + n.b2, L);
+    gc.tn(P.dh1, 2 * h0, P.xa, XS, nullptr, 2 * h0, nx, B, 1, 0, 0, part, grads + n.w1, grads + n.b1, L);
+    int rc = gc.rc ? gc.rc : (gc.njobs == NJOBS ? 0 : LRL_E_INVALID);
+    static const int hosts[3][3] = {{DW3, DW1, DW2}, {DW3, DW2, DW1}, {DW2, DW1, DW3}};
+    const int* host = g_timer.on ? hosts[0] : hosts[mode - 1];
+    if (!rc) rc = launch_jobs(jobs, {DWE3, DHE2, host[0]}, st);
+    if (!rc && g_timer.on) {
+      // the timed product (dW2: bench.py --full's roofline_update_gemm) alone, so its time keeps its meaning: dW1
+      // hosts dW2's rider, and the other two riders go in a launch of their own
+      rc = launch_jobs(jobs, {DWE2, DHE1}, st);
+      timer_begin(st);
+      if (!rc) rc = launch_jobs(jobs, {DW2}, st);
+      timer_end(st);
+      if (!rc) rc = launch_jobs(jobs, {DWE1, DW1}, st);
+    } else if (!rc) {
+      rc = launch_jobs(jobs, {DWE2, DHE1, host[1]}, st);
+      if (!rc) rc = launch_jobs(jobs, {DWE1, host[2]}, st);
+    }
+    if (rc) return lrl_set_error(rc, "lrl_ppo_forward_backward: backward GEMM launch failed");
+    launch_seg(L, st);
+    return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_ppo_forward_backward: launch failed");
+  }
   Fork* fk = fork_for_device(st);
   G ge{fk ? fk->st : st, g.part_end};
   if (fk) {
@@ -1993,17 +2069,17 @@ extern "C" int32_t lrl_gemm_f32(int32_t layout, int32_t epi, int32_t M, int32_t 
 }
 
 // ---- GEMM test entry point, the update's grouped / pitched operand forms ----
-extern "C" int32_t lrl_gemm_f32_ex(const lrl_gemm_desc* d, void* stream) {
+// The product a descriptor names as gemm_launch takes it (planes apart), and the split count of a TN product.
+static int32_t desc_job(const lrl_gemm_desc* d, GemmJob& job, int& splits) {
   if (!d || !d->A || !d->B || !d->C || d->M <= 0 || d->N <= 0 || d->K <= 0 || d->groups <= 0 || d->splits < 0)
     return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: bad argument");
-  hipStream_t st = static_cast<hipStream_t>(stream);
   const int layout = d->layout, epi = d->epi, groups = d->groups, M = d->M, N = d->N, K = d->K;
   if (d->path_out) *d->path_out = 0;
   GemmP p{};
   p.A = d->A; p.lda = d->lda; p.B = d->B; p.ldb = d->ldb; p.aux = d->aux; p.ld_aux = d->ld_aux;
   p.M = M; p.N = N; p.K = K; p.splits = 1;
   p.ga = d->ga; p.gb = d->gb; p.gaux = d->gaux;
-  int splits = 1;
+  splits = 1;
   if (layout == GEMM_TN) {
     // G::tn's layout: [split][group][M][N] partials, [split][group][M] bias partials behind them, one reduction
     if (epi != EPI_PARTIAL || d->planes) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: TN is epi 4, no planes");
@@ -2020,11 +2096,6 @@ extern "C" int32_t lrl_gemm_f32_ex(const lrl_gemm_desc* d, void* stream) {
     p.gc = (int64_t)M * N; p.ldc = N; p.part_stride = gmn;
     p.C = d->workspace;
     p.bias_part = d->workspace + (int64_t)splits * gmn;
-    if (int rc = gemm_launch(p, GEMM_TN, EPI_PARTIAL, groups, st)) return lrl_set_error(rc, "lrl_gemm_f32_ex: launch failed");
-    SegList L{};
-    L.s[L.n++] = Seg{d->workspace, d->C, gmn, gmn, splits, 1.f};
-    if (d->bias) L.s[L.n++] = Seg{p.bias_part, d->bias, gm, gm, splits, 1.f};
-    launch_seg(L, st);
   } else {
     if (layout != GEMM_NT && layout != GEMM_NN) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: layout is 0, 2 or 3");
     if (d->splits > 1 || epi == EPI_PARTIAL) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: NT / NN are not split");
@@ -2034,10 +2105,35 @@ extern "C" int32_t lrl_gemm_f32_ex(const lrl_gemm_desc* d, void* stream) {
     if ((epi == EPI_BIAS || epi == EPI_BIAS_ELU || epi == EPI_BIAS_TANH) && !d->bias)
       return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: epi 1 / 2 / 5 need bias");
     p.C = d->C; p.ldc = d->ldc; p.gc = d->gc; p.bias = d->bias; p.gbias = d->gbias; p.a_rows = d->rows;
+  }
+  job = GemmJob{p, layout, epi, groups};
+  return 0;
+}
+// the reduction of a TN descriptor's partials into its C (and db = bias)
+static void desc_reduce(const lrl_gemm_desc* d, const GemmJob& job, int splits, SegList& L) {
+  if (job.layout != GEMM_TN) return;
+  const int64_t gmn = (int64_t)d->groups * d->M * d->N, gm = (int64_t)d->groups * d->M;
+  L.s[L.n++] = Seg{d->workspace, d->C, gmn, gmn, splits, 1.f};
+  if (d->bias) L.s[L.n++] = Seg{job.p.bias_part, d->bias, gm, gm, splits, 1.f};
+}
+
+extern "C" int32_t lrl_gemm_f32_ex(const lrl_gemm_desc* d, void* stream) {
+  GemmJob job;
+  int splits = 1;
+  if (int32_t rc = desc_job(d, job, splits)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  GemmP& p = job.p;
+  const int layout = job.layout, epi = job.epi, groups = job.groups;
+  if (layout == GEMM_TN) {
+    if (int rc = gemm_launch(p, GEMM_TN, EPI_PARTIAL, groups, st)) return lrl_set_error(rc, "lrl_gemm_f32_ex: launch failed");
+    SegList L{};
+    desc_reduce(d, job, splits, L);
+    launch_seg(L, st);
+  } else {
     PlaneJob j{};
     if (d->planes) {
       j.W = d->B; j.ldw = d->ldb; j.gsrc = d->gb; j.groups = groups; j.trans = layout == GEMM_NN ? 1 : 0;
-      j.rows = layout == GEMM_NN ? K : N; j.cols = layout == GEMM_NN ? N : K;
+      j.rows = layout == GEMM_NN ? d->K : d->N; j.cols = layout == GEMM_NN ? d->N : d->K;
       j.dst = reinterpret_cast<uint16_t*>(d->workspace);
       if (!d->workspace || plane_elems(j) > 2 * d->workspace_floats)
         return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: workspace too small for the planes");
@@ -2052,6 +2148,29 @@ extern "C" int32_t lrl_gemm_f32_ex(const lrl_gemm_desc* d, void* stream) {
   if (d->path_out) *d->path_out = gemm_last_path();
   if (d->splits_out) *d->splits_out = splits;
   return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_gemm_f32_ex: launch failed");
+}
+
+// ---- test entry point of the multi-problem launch (gemm_launch_multi) ----
+extern "C" int32_t lrl_gemm_f32_multi(const lrl_gemm_desc* d, int32_t n, void* stream) {
+  if (!d || n < 2 || n > MAX_MULTI_JOBS) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_multi: 2 or 3 descriptors");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  GemmJob jobs[MAX_MULTI_JOBS];
+  int splits[MAX_MULTI_JOBS];
+  for (int i = 0; i < n; ++i) {
+    if (d[i].planes) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_multi: no planes");
+    if (int32_t rc = desc_job(&d[i], jobs[i], splits[i])) return rc;
+  }
+  const int r = gemm_launch_multi(jobs, n, st);
+  if (r < 0) return lrl_set_error(r, "lrl_gemm_f32_multi: launch failed");
+  if (r == 0) return 1;  // not one of the sets on offer: nothing was launched
+  SegList L{};
+  for (int i = 0; i < n; ++i) {
+    desc_reduce(&d[i], jobs[i], splits[i], L);
+    if (d[i].splits_out) *d[i].splits_out = splits[i];
+  }
+  launch_seg(L, st);
+  if (d[n - 1].path_out) *d[n - 1].path_out = gemm_last_path();
+  return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_gemm_f32_multi: launch failed");
 }
 
 // ---- timing hook of the dominant update product (bench.py roofline) ----

@@ -130,6 +130,8 @@ class LrlGemmDesc(C.Structure):
                [("path_out", C.POINTER(i32)), ("splits_out", C.POINTER(i32))]
 
 
+GEMM_MULTI_NOT_ELIGIBLE = 1  # lrl_gemm_f32_multi: the descriptors are not a set it offers, nothing was launched
+
 # family ids of the path report (LRL_GEMM_PATH_* of include/lrl.h): report = family | bm << 8 | bn << 16 | interior << 24
 GEMM_FAMILIES = {1: "x6p", 2: "x6t", 3: "x6", 4: "x6d", 5: "glds", 6: "glds32", 7: "glds_tn", 8: "thin16",
                  9: "thin32", 10: "staged"}
@@ -217,7 +219,7 @@ def lib():
                      "lrl_ppo_act", "lrl_abi_version", "lrl_device_count", "lrl_gae_partial", "lrl_adv_normalize",
                      "lrl_sim_reset_idx_ex", "lrl_sim_observe_idx", "lrl_sim_set_step_counter", "lrl_ppo_forward_backward",
                      "lrl_ppo_optimizer_step", "lrl_ppo_adaptation_forward_backward", "lrl_ppo_adaptation_step",
-                     "lrl_gemm_f32", "lrl_gemm_f32_ex", "lrl_ppo_timing", "lrl_ppo_act_student", "lrl_sim_set_terrain",
+                     "lrl_gemm_f32", "lrl_gemm_f32_ex", "lrl_gemm_f32_multi", "lrl_ppo_timing", "lrl_ppo_act_student", "lrl_sim_set_terrain",
                      "lrl_sim_terrain_curriculum", "lrl_sim_inject_reset_uniforms", "lrl_sim_inject_push_uniforms", "lrl_sim_timing",
                      "lrl_sim_self_contact_stats", "lrl_ppo_store_step", "lrl_curriculum_sample",
                      "lrl_curriculum_update_weights", "lrl_rows_mean_zero", "lrl_sim_step_code",
