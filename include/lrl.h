@@ -211,8 +211,9 @@ typedef struct lrl_env_params {
   /* Cfg.sim.physx.solver_type (legged_robot_config.py:247; 1 = TGS): the contact / limit solve runs solver_iterations
    * sub-iterations of h = sim_dt / solver_iterations, each sweeping the rows once with targets from the separations
    * moved by the motion so far, and positions integrate the accumulated motion.  0 = PGS: the
-   * iterations sweep the whole sub-step with the start targets.  Plane ground only (the terrain-mesh build solves
-   * with PGS and the host passes 0 there). */
+   * iterations sweep the whole sub-step with the start targets.  With terrain_mesh = 1 the value selects the env
+   * kernel's terrain-mesh TGS build; the host passes 0 there unless Cfg.sim.physx.terrain_solver_type is 1
+   * (lrl/params.py: the mesh solves with PGS by default). */
   int32_t solver_tgs;
   /* observation-layout switches (compute_observations :342-417; all 0 = the layout above):
    * observe_only_ang_vel / observe_only_lin_vel (Cfg.env, :370-376): base-frame angular / linear velocity x scale in
@@ -665,6 +666,9 @@ int32_t lrl_debug_sim_garbage(lrl_sim* s, uint32_t mode, uint32_t pattern);
  * copies the arena, runs lrl_sim_step, restores the copy and the counter — lrl_sim_set_step_counter — and runs it
  * again).  Any out-pointer may be NULL. */
 int32_t lrl_debug_sim_arena(lrl_sim* s, void** arena, int64_t* bytes, int64_t* step_counter);
+/* The dynamic LDS, in bytes, of the env step kernel build this sim launches (the plane build, the terrain-mesh PGS
+ * build, or the terrain-mesh TGS build: terrain_mesh with solver_tgs and solver_iterations > 0); at most 163,840. */
+int32_t lrl_debug_sim_lds_bytes(lrl_sim* s);
 
 /* Test entry point of the GEMM the update is built from: C = op(A) op(B) with
  * layout 0 (NT: C[m][n] = sum_k A[m][k] B[n][k]), 2 (NN: sum_k A[m][k] B[k][n]),

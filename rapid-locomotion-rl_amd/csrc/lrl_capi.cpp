@@ -28,7 +28,8 @@ extern "C" int lrl_set_error(int code, const char* msg) { return fail(code, "%s"
   } while (0)
 
 extern "C" {
-hipError_t lrl_launch_env_step(const KParams*, const KState*, int, const float*, uint32_t, int64_t, int, hipStream_t);
+hipError_t lrl_launch_env_step(const KParams*, const KState*, int, const float*, uint32_t, int64_t, int, int,
+                               hipStream_t);
 hipError_t lrl_launch_observe(const KParams*, const KState*, const int32_t*, int32_t, const int32_t*, uint32_t, int64_t,
                               hipStream_t);
 hipError_t lrl_env_kernel_setup(int lds_bytes);
@@ -67,6 +68,7 @@ struct lrl_sim {
   void* arena = nullptr;
   size_t arena_bytes = 0;
   int lds_bytes = 0;
+  int mesh_tgs = 0;  // the env kernel's terrain-mesh TGS build (terrain_mesh, solver_tgs, solver_iterations > 0)
   int64_t step_counter = 0;
   lrl_tensor t[LRL_T_NUM];
   int32_t* d_body_leg = nullptr;
@@ -395,14 +397,19 @@ int32_t lrl_sim_create(const lrl_model* model, const lrl_env_params* params, int
   HIPCHECK(hipMemcpy(s->d_foot_xyz, model->foot_xyz, sizeof(float) * 12, hipMemcpyHostToDevice));
   // env step kernel LDS: wg_envs envs per workgroup: leg blocks + contact rows, or the obs tiles
   const int wg_envs = params->terrain_mesh ? LRL_ENV_WG_ENVS_MESH : LRL_ENV_WG_ENVS_FLAT;
-  const int legf = params->terrain_mesh ? LRL_LEGF_MESH : LRL_LEGF_FLAT, nsf = params->terrain_mesh ? LRL_NSF_MESH : LRL_NSF_FLAT;
+  s->mesh_tgs = params->terrain_mesh && params->solver_tgs && params->solver_iterations > 0;
+  const int legf = s->mesh_tgs ? LRL_LEGF_MESH_TGS : params->terrain_mesh ? LRL_LEGF_MESH : LRL_LEGF_FLAT;
+  const int nsf = params->terrain_mesh ? LRL_NSF_MESH : LRL_NSF_FLAT;
   int lds_contacts = (4 * legf + model->num_spheres * nsf) * wg_envs * 4;  // LEGF, NSF of lrl_env.hip
   // terrain query vertex block, float4 [16][lanes]; the joint-limit rows (12 x 19 fields per env) alias it after the
   // queries, and have their own region on the plane
-  lds_contacts += params->terrain_mesh ? 16 * LRL_ENV_LANES * 16 : LRL_NUM_DOF * 19 * wg_envs * 4;
+  // (the mesh TGS build: that block and the work list as one scratch that also takes the restitution targets)
+  lds_contacts += s->mesh_tgs           ? LRL_MESH_TGS_SCRATCH(model->num_spheres) * 4
+                  : params->terrain_mesh ? 16 * LRL_ENV_LANES * 16
+                                         : LRL_NUM_DOF * LRL_LIMF * wg_envs * 4;
   lds_contacts += (4 * (int)(sizeof(KLeg) / 4) + 5 * model->num_spheres) * 4;  // staged model tables (Lds::ktab)
   lds_contacts += (40 + s->hk.self_npairs + 1) * 4;  // + the self-collision groups and pairs
-  if (params->terrain_mesh) lds_contacts += LRL_ENV_LANES * 20;  // + the terrain query work list (Lds::wl)
+  if (params->terrain_mesh && !s->mesh_tgs) lds_contacts += LRL_ENV_LANES * 20;  // + the terrain query work list (Lds::wl)
   int lds_tiles = (NO + LRL_NUM_PRIV + LRL_MAX_REWARD_TERMS) * wg_envs * 4;  // obs / priv tiles + reward rows
   s->lds_bytes = lds_contacts > lds_tiles ? lds_contacts : lds_tiles;
   if (s->lds_bytes > 160 * 1024) return fail(LRL_E_INVALID, "LDS budget exceeded (%d B)", s->lds_bytes);
@@ -602,7 +609,7 @@ int32_t lrl_sim_step(lrl_sim* s, const float* actions, uint32_t flags, void* str
     tp = &s->ev[s->ev_used++];
     HIPCHECK(hipEventRecord(tp->first, (hipStream_t)stream));
   }
-  HIPCHECK(lrl_launch_env_step(s->dk, &s->S, s->lds_bytes, actions, flags, s->step_counter, s->hk.p.terrain_mesh,
+  HIPCHECK(lrl_launch_env_step(s->dk, &s->S, s->lds_bytes, actions, flags, s->step_counter, s->hk.p.terrain_mesh, s->mesh_tgs,
                                (hipStream_t)stream));
   if (tp) HIPCHECK(hipEventRecord(tp->second, (hipStream_t)stream));
   return 0;
@@ -614,6 +621,11 @@ int32_t lrl_debug_sim_garbage(lrl_sim* s, uint32_t mode, uint32_t pattern) {
   s->garbage_mode = mode;
   s->garbage_pat = pattern;
   return 0;
+}
+
+int32_t lrl_debug_sim_lds_bytes(lrl_sim* s) {
+  if (!s) return fail(LRL_E_INVALID, "null sim");
+  return s->lds_bytes;
 }
 
 int32_t lrl_debug_sim_arena(lrl_sim* s, void** arena, int64_t* bytes, int64_t* step_counter) {

@@ -40,17 +40,27 @@
 // loops over max-over-envs contact counts run over 4 envs instead of 16; 1,024 single-wave workgroups fill every
 // SIMD of the chip (the 16-env form leaves 3 of each CU's 4 SIMDs idle).  The terrain-mesh build keeps 16 envs per
 // wave: its rows do not fit 4 workgroups' LDS per CU.
-#ifdef LRL_ENV_FLAT_TU
+// Terrain-mesh TGS build (lrl_env_mesh_tgs.hip includes this file with LRL_ENV_MESH_TGS_TU): the mesh layout, with the
+// TGS solver of the plane build compiled in unconditionally (lrl_launch_env_step launches it only for solver_tgs with
+// solver_iterations > 0) and room for its fields (lrl_kparams.h); the PGS mesh build stays as it is.
+// ENV_TGS: the build's solver — 0 PGS only, 1 PGS or TGS by KParams::p.solver_tgs, 2 TGS only.
+#if defined(LRL_ENV_FLAT_TU)
 #define ENVS LRL_ENV_WG_ENVS_FLAT
 #define LRL_ENV_NS flat
+#define ENV_TGS 1
+#elif defined(LRL_ENV_MESH_TGS_TU)
+#define ENVS (BLOCK / QL)
+#define LRL_ENV_NS mesh_tgs
+#define ENV_TGS 2
 #else
 #define ENVS (BLOCK / QL)
 #define LRL_ENV_NS mesh
+#define ENV_TGS 0
 #endif
 #define MIRROR (BLOCK / (QL * ENVS))  // quads per env
 static_assert(MIRROR == 1 || MIRROR == 4, "an env has one quad or four mirrored quads");
 #define NSF (MIRROR > 1 ? LRL_NSF_FLAT : LRL_NSF_MESH)  // LDS fields per contact sphere (map above contact_setup)
-#define LIMF 19  // LDS fields per joint-limit row (map above limit_setup)
+#define LIMF LRL_LIMF  // LDS fields per joint-limit row (map above limit_setup)
 
 namespace lrl {
 inline namespace LRL_ENV_NS {
@@ -198,8 +208,8 @@ __device__ __forceinline__ float sv_get(const SV& s, int r) {
 //   36..41 D^-1 (00 11 22 01 02 12)   42..44 per-joint bias / solve scratch
 //   45..47 leg joint rates at the start of the contact solve   48..50 Y = sum of D^-1 p_l over the
 //   impulses applied to this leg (lazy propagation: qd_l = qd0_l + Y_l - K_l (v_b - v_b0))
-//   51..53 (plane build, TGS) dz = sum over the sub-iterations of h (q0_l + Y_l) = the leg's joint motion + K_l dx_b
-#define LEGF (MIRROR > 1 ? LRL_LEGF_FLAT : LRL_LEGF_MESH)
+//   51..53 (TGS builds) dz = sum over the sub-iterations of h (q0_l + Y_l) = the leg's joint motion + K_l dx_b
+#define LEGF (MIRROR > 1 ? LRL_LEGF_FLAT : ENV_TGS == 2 ? LRL_LEGF_MESH_TGS : LRL_LEGF_MESH)
 #define LF_DZ 51
 #define LI(r, c) ((r) * ((r) + 1) / 2 + (c))
 
@@ -244,6 +254,14 @@ struct Lds {
   __device__ __forceinline__ float* sp(int s) const { return base + (sph_off + s * NSF) * ENVS + es; }
   __device__ __forceinline__ float* lp(int l) const { return base + l * LEGF * ENVS + es; }
   __device__ __forceinline__ float* lm(int r) const { return base + (lim_off + r * LIMF) * ENVS + es; }
+  // (TGS) the restitution target of sphere s: the row's last field on the plane; on the mesh [sphere][env slot] after
+  // the joint-limit rows, in the query scratch (LRL_MESH_TGS_SCRATCH, lrl_kparams.h)
+  __device__ __forceinline__ float* br(int s) const {
+    if constexpr (MIRROR > 1)
+      return sp(s) + (NSF - 1) * ENVS;
+    else
+      return base + (lim_off + LRL_NUM_DOF * LIMF + s) * ENVS + es;
+  }
   __device__ __forceinline__ float Kx(int l, int j, int r) const { return leg(l, 18 + 6 * j + r); }
   __device__ __forceinline__ float Di(int l, int k) const { return leg(l, 36 + k); }
 };
@@ -563,15 +581,14 @@ __device__ __forceinline__ void contact_frame(V3 n, V3& t1, V3& t2) {
 //          g_d = [x x n_d, n_d] - K_L^T h_d   (the same row maps an impulse to the base: r = sum_d lambda_d g_d)
 //   31..39 h_d = C_L^T n_d (joint-rate row; C_L = joint directions of the carrying joints)
 //   40..57 z_d = S^-1 g_d (base-velocity change per unit impulse)   58..66 e_d = D_L^-1 h_d (change of Y_L)
-//   (plane build, TGS) field 9 holds the sub-step-start separation instead of the velocity target, 67 the restitution
-//   target (-1e30 without one); each sub-iteration forms the target from sep_0 + J_n dx (below)
+//   (TGS) field 9 holds the sub-step-start separation instead of the velocity target, Lds::br the restitution target
+//   (-1e30 without one; the plane build's field 67); each sub-iteration forms the target from sep_0 + J_n dx (below)
 // so one Gauss-Seidel update is u_d = g_d . v_b + h_d . (q0_L + Y_L), the cone projection, and
 // v_b += sum_d dlambda_d z_d,  Y_L += sum_d dlambda_d e_d  — short independent dot products.
 #define SF_G 13
 #define SF_H 31
 #define SF_Z 40
 #define SF_E 58
-#define SF_BR 67
 
 // apply a world-frame impulse change dl = (n, t1, t2) of sphere s (leg lsel) to v_b and Y_lsel (every read
 // before the first store, so the rows arrive in one LDS round trip)
@@ -813,7 +830,7 @@ template <bool B>
 struct BoolC {
   static constexpr bool value = B;
 };
-// TGS (plane build, solver_type 1): the sub-iteration's motion so far, dx = (dx_b spread over the quad as v_b is, dz of
+// TGS (solver_type 1): the sub-iteration's motion so far, dx = (dx_b spread over the quad as v_b is, dz of
 // the legs in LDS), and what turns a separation into a target (h = dt / iterations)
 struct Tgs {
   float dxo0, dxo1, ih, baum, maxdep;
@@ -854,7 +871,7 @@ __device__ __forceinline__ void contact_pgs_q(const Lds& M, int s, int lsel, flo
   float b;
   if constexpr (TGS) {  // field 9 = sep0, the restitution target a floor under the sub-iteration's target
     const float dz = lg[LF_DZ * ENVS];
-    b = fmaxf(tgs_target(T, b9, g0[0] * T.dxo0 + g1[0] * T.dxo1 + (hj ? hv[0] * dz : 0.f)), rs[SF_BR * ENVS]);
+    b = fmaxf(tgs_target(T, b9, g0[0] * T.dxo0 + g1[0] * T.dxo1 + (hj ? hv[0] * dz : 0.f)), *M.br(s));
   } else {
     b = b9;
   }
@@ -1473,10 +1490,10 @@ __device__ void substep(const KParams* __restrict__ K, Body& st, const float* ta
   const SphLegs SL = sph_legs(K);
   const lrl_env_params& P = K->p;
   const float dt = P.sim_dt, idt = frcp(dt);
-  // TGS (legged_robot_config.py:247 solver_type 1; host: plane only) — the oracle's restatement, lrl_oracle.c
-  // physics_substep: N sub-iterations of h = dt / N, targets from the separations moved by the motion so far, positions
-  // from the accumulated motion
-  const bool tgs = MIRROR > 1 && P.solver_tgs != 0 && P.solver_iterations > 0;
+  // TGS (legged_robot_config.py:247 solver_type 1; on the mesh only with terrain_solver_type 1, in the build of its own) —
+  // the oracle's restatement, lrl_oracle.c physics_substep: N sub-iterations of h = dt / N, targets from the separations
+  // moved by the motion so far, positions from the accumulated motion
+  const bool tgs = ENV_TGS == 2 || (ENV_TGS == 1 && P.solver_tgs != 0 && P.solver_iterations > 0);
   const M3 R = quat_mat(st.quat[0], st.quat[1], st.quat[2], st.quat[3]);
   const V3 wb = mulT(R, v3(st.W[0], st.W[1], st.W[2]));
   const V3 vb = mulT(R, v3(st.V[0], st.V[1], st.V[2])) - cross(wb, cb);
@@ -1518,6 +1535,10 @@ __device__ void substep(const KParams* __restrict__ K, Body& st, const float* ta
       for (int j = 0; j < 3; ++j) u = u + st.qd[j] * c[j];
     }
     const float u0 = dot(nb, u);
+    if constexpr (ENV_TGS == 2) {  // field 9 keeps the query's separation; the sub-iterations form the targets
+      *M.br(s) = (u0 < -P.bounce_threshold_velocity && rest > 0.f) ? -rest * u0 : -1e30f;
+      return;
+    }
     float tgt = sep >= 0.f ? -sep * idt : fminf(-P.baumgarte * sep * idt, P.max_depenetration_velocity);
     if (u0 < -P.bounce_threshold_velocity && rest > 0.f) tgt = fmaxf(tgt, -rest * u0);
     M.sph(s, 9) = tgt;
@@ -1572,10 +1593,10 @@ __device__ void substep(const KParams* __restrict__ K, Body& st, const float* ta
       }
       const float u0 = dot(Rz, u);
       const bool bounce = u0 < -P.bounce_threshold_velocity && rest > 0.f;
-      if constexpr (MIRROR > 1) {
+      if constexpr (ENV_TGS != 0) {
         if (tgs) {  // separation and restitution target; the sub-iterations form the targets
           M.sph(s, 9) = sep;
-          M.sph(s, SF_BR) = bounce ? -rest * u0 : -1e30f;
+          *M.br(s) = bounce ? -rest * u0 : -1e30f;
           return;
         }
       }
@@ -1925,7 +1946,7 @@ __device__ void substep(const KParams* __restrict__ K, Body& st, const float* ta
       for (int r = 0; r < 6; ++r) k += M.Kx(l, j, r) * vb0[r];
       M.leg(l, 45 + j) = nu[6 + j] + k;
       M.leg(l, 48 + j) = 0.f;
-      if constexpr (MIRROR > 1) M.leg(l, LF_DZ + j) = 0.f;
+      if constexpr (ENV_TGS != 0) M.leg(l, LF_DZ + j) = 0.f;
     }
   }
   // Delassus rows of the active spheres, each in the lane that owns the sphere (only spheres active in some
@@ -2026,7 +2047,9 @@ __device__ void substep(const KParams* __restrict__ K, Body& st, const float* ta
         }
       }
     };
-    if constexpr (MIRROR > 1) {
+    if constexpr (ENV_TGS == 2) {
+      sweeps(BoolC<true>{});
+    } else if constexpr (ENV_TGS == 1) {
       if (tgs)
         sweeps(BoolC<true>{});
       else
@@ -2319,9 +2342,12 @@ __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restri
   // leg blocks first, then the contact rows, (terrain: the query's vertex block), then the model tables
   const int nsph = K->num_spheres;
   static_assert(LRL_NUM_DOF * LIMF * ENVS <= 64 * BLOCK, "joint-limit rows must fit the terrain vertex blocks");
-  float* const ktab = lds + (4 * LEGF + nsph * NSF) * ENVS + (TERR ? 64 * BLOCK : LRL_NUM_DOF * LIMF * ENVS);
+  // (mesh TGS build: the query's work list ends the scratch, ahead of the tables, so that the restitution targets can
+  // run from the vertex blocks' tail into its dead part: LRL_MESH_TGS_SCRATCH)
+  const int scratch = ENV_TGS == 2 ? LRL_MESH_TGS_SCRATCH(nsph) : TERR ? 64 * BLOCK : LRL_NUM_DOF * LIMF * ENVS;
+  float* const ktab = lds + (4 * LEGF + nsph * NSF) * ENVS + scratch;
   const Lds M{lds, 4 * LEGF, es, ktab, nsph, 4 * LEGF + nsph * NSF,
-              ktab + ((4 * KLEGF + 5 * nsph + 40 + K->self_npairs + 1) & ~1)};
+              ENV_TGS == 2 ? ktab - 5 * BLOCK : ktab + ((4 * KLEGF + 5 * nsph + 40 + K->self_npairs + 1) & ~1)};
   {
     const float* src = reinterpret_cast<const float*>(K->leg);
     for (int i = lane; i < 4 * KLEGF; i += BLOCK) M.ktab[i] = src[i];
@@ -2881,19 +2907,64 @@ extern "C" hipError_t lrl_launch_env_step_flat(const KParams* K, const KState* S
                      actions, flags, step_counter);
   return hipGetLastError();
 }
+#elif defined(LRL_ENV_MESH_TGS_TU)
+// the terrain-mesh TGS build's entry points (lrl_env_mesh_tgs.hip); lrl_launch_env_step & co. dispatch to them
+extern "C" int lrl_debug_env_profile_mesh_tgs(unsigned long long* out, int reset) {
+#ifdef LRL_ENV_PROFILE
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(lrl::g_env_prof), sizeof(unsigned long long) * 24) != hipSuccess) return -2;
+  if (reset) {
+    unsigned long long z[24] = {0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(lrl::g_env_prof), z, sizeof(z)) != hipSuccess) return -2;
+  }
+  return 24;
+#else
+  (void)out;
+  (void)reset;
+  return 0;
+#endif
+}
+
+extern "C" int lrl_debug_env_buffer_mesh_tgs(float* buf) {
+#ifdef LRL_ENV_DEBUG
+  return hipMemcpyToSymbol(HIP_SYMBOL(lrl::g_env_dbg), &buf, sizeof(buf)) == hipSuccess ? 1 : -2;
+#else
+  (void)buf;
+  return 0;
+#endif
+}
+
+extern "C" hipError_t lrl_env_kernel_setup_mesh_tgs(int lds_bytes) {
+  return hipFuncSetAttribute((const void*)lrl::env_step_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             lds_bytes);
+}
+
+extern "C" hipError_t lrl_launch_env_step_mesh_tgs(const KParams* K, const KState* S, int lds_bytes,
+                                                   const float* actions, uint32_t flags, int64_t step_counter,
+                                                   hipStream_t stream) {
+  hipLaunchKernelGGL(lrl::env_step_kernel<true>, dim3(S->stride / ENVS), dim3(BLOCK), lds_bytes, stream, K, *S,
+                     actions, flags, step_counter);
+  return hipGetLastError();
+}
 #else
 extern "C" int lrl_debug_env_profile_flat(unsigned long long* out, int reset);
 extern "C" hipError_t lrl_env_kernel_setup_flat(int lds_bytes);
 extern "C" hipError_t lrl_launch_env_step_flat(const KParams* K, const KState* S, int lds_bytes, const float* actions,
                                                uint32_t flags, int64_t step_counter, hipStream_t stream);
+extern "C" int lrl_debug_env_profile_mesh_tgs(unsigned long long* out, int reset);
+extern "C" int lrl_debug_env_buffer_mesh_tgs(float* buf);
+extern "C" hipError_t lrl_env_kernel_setup_mesh_tgs(int lds_bytes);
+extern "C" hipError_t lrl_launch_env_step_mesh_tgs(const KParams* K, const KState* S, int lds_bytes,
+                                                   const float* actions, uint32_t flags, int64_t step_counter,
+                                                   hipStream_t stream);
 
-// the sum of the two builds' timers (a simulation runs one of them)
+// the sum of the three builds' timers (a simulation runs one of them)
 extern "C" int lrl_debug_env_profile(unsigned long long* out, int reset) {
 #ifdef LRL_ENV_PROFILE
-  unsigned long long f[24];
+  unsigned long long f[24], g[24];
   if (lrl_debug_env_profile_flat(f, reset) != 24) return -2;
+  if (lrl_debug_env_profile_mesh_tgs(g, reset) != 24) return -2;
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(lrl::g_env_prof), sizeof(unsigned long long) * 24) != hipSuccess) return -2;
-  for (int i = 0; i < 24; ++i) out[i] += f[i];
+  for (int i = 0; i < 24; ++i) out[i] += f[i] + g[i];
   if (reset) {
     unsigned long long z[24] = {0};
     if (hipMemcpyToSymbol(HIP_SYMBOL(lrl::g_env_prof), z, sizeof(z)) != hipSuccess) return -2;
@@ -2908,6 +2979,7 @@ extern "C" int lrl_debug_env_profile(unsigned long long* out, int reset) {
 
 extern "C" int lrl_debug_env_buffer(float* buf) {
 #ifdef LRL_ENV_DEBUG
+  if (lrl_debug_env_buffer_mesh_tgs(buf) != 1) return -2;
   return hipMemcpyToSymbol(HIP_SYMBOL(lrl::g_env_dbg), &buf, sizeof(buf)) == hipSuccess ? 1 : -2;
 #else
   (void)buf;
@@ -2917,6 +2989,8 @@ extern "C" int lrl_debug_env_buffer(float* buf) {
 
 extern "C" hipError_t lrl_env_kernel_setup(int lds_bytes) {
   hipError_t e = lrl_env_kernel_setup_flat(lds_bytes);
+  if (e != hipSuccess) return e;
+  e = lrl_env_kernel_setup_mesh_tgs(lds_bytes);
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)lrl::env_step_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              lds_bytes);
@@ -3046,9 +3120,12 @@ __global__ __launch_bounds__(256) void observe_kernel(const KParams* __restrict_
 }  // namespace LRL_ENV_NS
 }  // namespace lrl
 
+// mesh_tgs: the sim's parameters ask for TGS on the mesh (terrain_mesh, solver_tgs, solver_iterations > 0)
 extern "C" hipError_t lrl_launch_env_step(const KParams* K, const KState* S, int lds_bytes, const float* actions,
-                                          uint32_t flags, int64_t step_counter, int terrain_mesh, hipStream_t stream) {
+                                          uint32_t flags, int64_t step_counter, int terrain_mesh, int mesh_tgs,
+                                          hipStream_t stream) {
   if (!terrain_mesh) return lrl_launch_env_step_flat(K, S, lds_bytes, actions, flags, step_counter, stream);
+  if (mesh_tgs) return lrl_launch_env_step_mesh_tgs(K, S, lds_bytes, actions, flags, step_counter, stream);
   hipLaunchKernelGGL(lrl::env_step_kernel<true>, dim3(S->stride / ENVS), dim3(BLOCK), lds_bytes, stream, K, *S,
                      actions, flags, step_counter);
   return hipGetLastError();
@@ -3061,4 +3138,4 @@ extern "C" hipError_t lrl_launch_observe(const KParams* K, const KState* S, cons
                      K, *S, ids, n, dn, flags, step_counter);
   return hipGetLastError();
 }
-#endif  // LRL_ENV_FLAT_TU
+#endif  // LRL_ENV_FLAT_TU / LRL_ENV_MESH_TGS_TU

@@ -19,12 +19,25 @@
 #define LRL_ENV_WG_ENVS_MESH (LRL_ENV_LANES / 4)
 #define LRL_ENV_WG_ENVS_FLAT (LRL_ENV_LANES / 16)
 // LDS fields per leg block / per contact-sphere row of the env kernel (lrl_env.hip): the plane build carries the TGS
-// solver's extra fields (the leg's accumulated joint-space motion dz, a contact's restitution target), the terrain-mesh
-// build has no room for them (its 16-env workgroup fills the CU's LDS) and solves with PGS
+// solver's extra fields (the leg's accumulated joint-space motion dz, a contact's restitution target).  The terrain-mesh
+// PGS build has neither (its 16-env workgroup fills the CU's LDS).  The terrain-mesh TGS build (lrl_env_mesh_tgs.hip,
+// Cfg.sim.physx.terrain_solver_type 1) has dz in its leg blocks and keeps the restitution targets out of the rows, in
+// LDS that is dead during the solve: after the joint-limit rows in the terrain query's scratch (below)
 #define LRL_LEGF_MESH 51
+#define LRL_LEGF_MESH_TGS 54
 #define LRL_LEGF_FLAT 54
 #define LRL_NSF_MESH 67
 #define LRL_NSF_FLAT 68
+#define LRL_LIMF 19  // LDS fields per joint-limit row
+// The mesh TGS build's query scratch, in floats, for a model of nsph spheres: the vertex blocks (float4 [16][lanes])
+// followed by the query work list (5 floats per lane, its last 2 per lane the hit masks the activation reads).  Once a
+// sub-step's queries are done the joint-limit rows alias the start of it, as in the PGS build, and the restitution
+// targets ([sphere][env slot]) follow them; they may run over the dead part of the work list but not over the hit
+// masks, so a model with more spheres than that leaves room for gets a longer scratch.
+#define LRL_MESH_TGS_SCRATCH(nsph)                                                                       \
+  ((64 + 5) * LRL_ENV_LANES > (LRL_NUM_DOF * LRL_LIMF + (nsph)) * LRL_ENV_WG_ENVS_MESH + 2 * LRL_ENV_LANES \
+       ? (64 + 5) * LRL_ENV_LANES                                                                         \
+       : (LRL_NUM_DOF * LRL_LIMF + (nsph)) * LRL_ENV_WG_ENVS_MESH + 2 * LRL_ENV_LANES)
 
 struct KLeg {
   float xyz[3][3];   // joint origin in the parent frame

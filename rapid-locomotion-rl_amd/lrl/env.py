@@ -506,6 +506,12 @@ class LeggedRobotEnv:
             pass
 
     @property
+    def solver(self):
+        """The contact solver the env kernel runs: "tgs" (Cfg.sim.physx.solver_type 1 on the plane; on a terrain mesh
+        only with Cfg.sim.physx.terrain_solver_type 1 as well) or "pgs"."""
+        return "tgs" if self._P.solver_tgs and self._P.solver_iterations > 0 else "pgs"
+
+    @property
     def reset_buf(self):
         return self._reset_u8.view(torch.bool)
 

@@ -112,16 +112,24 @@ def body_sets(cfg, robot):
     return feet, pen, term
 
 
+def terrain_solver(cfg, override=None):
+    """Cfg.sim.physx.terrain_solver_type (project-only; absent = 0), or the override."""
+    return int(getattr(cfg.sim.physx, "terrain_solver_type", 0) if override is None else override)
+
+
 def build_params(cfg, robot, auto_reset=False, solver_iterations=None, baumgarte=0.2, terrain_mesh=0,
-                 joint_limits=True, joint_limit_margin=0.02, self_collisions=None, solver_type=None):
+                 joint_limits=True, joint_limit_margin=0.02, self_collisions=None, solver_type=None,
+                 terrain_solver_type=None):
     """terrain_mesh: 1 when the sim collides with a generated height field / trimesh (lrl_sim_set_terrain),
     0 for the plane z = 0 (mesh_type 'plane', or a trimesh whose heights are all zero).
     joint_limits: enforce the URDF joint position limits in the contact solve (Isaac Gym / PhysX always enforces
     them for limited revolute joints: the reference has no switch); joint_limit_margin: activation window, rad.
     self_collisions: None follows Cfg.asset.self_collisions (0 = enabled, Isaac Gym's filter semantics: both presets
     enable it, mini_cheetah_config.py:44, go1_config.py:44); True / False override.
-    solver_type: None follows Cfg.sim.physx.solver_type (1 = TGS, legged_robot_config.py:247; 0 = PGS); the
-    terrain-mesh build always solves with PGS."""
+    solver_type: None follows Cfg.sim.physx.solver_type (1 = TGS, legged_robot_config.py:247; 0 = PGS).
+    terrain_solver_type: None follows the project-only key Cfg.sim.physx.terrain_solver_type (absent = 0).  0: the
+    terrain mesh solves with PGS whatever solver_type says; 1: the mesh follows solver_type (TGS when it is 1, the
+    env kernel's terrain-mesh TGS build).  On the plane it changes nothing."""
     dt = derived(cfg)
     P = _abi.LrlEnvParams()
     dof_names = robot["dof_names"]
@@ -236,7 +244,8 @@ def build_params(cfg, robot, auto_reset=False, solver_iterations=None, baumgarte
         # torch_rand_float(-max, max, (k, 2)) = (max - -max) * torch.rand + -max (legged_robot.py:763-764)
         push_robots=int(bool(dr0.push_robots)), push_interval=int(cfg.domain_rand.push_interval),
         push_lo=-push_max, push_span=push_max - (-push_max),
-        solver_tgs=int((physx.solver_type if solver_type is None else solver_type) == 1 and not terrain_mesh),
+        solver_tgs=int((physx.solver_type if solver_type is None else solver_type) == 1 and
+                       (not terrain_mesh or terrain_solver(cfg, terrain_solver_type) == 1)),
         observe_only_ang_vel=int(bool(cfg.env.observe_only_ang_vel)),
         observe_only_lin_vel=int(bool(cfg.env.observe_only_lin_vel)), observe_yaw=int(bool(cfg.env.observe_yaw)),
         global_reference=int(bool(cfg.commands.global_reference)),

@@ -2,8 +2,10 @@
 ml_logger resolve to the package's stand-ins — and the same calls (logger.configure / log_text / log_params,
 VelocityTrackingEasyEnv, HistoryWrapper, Runner(env, device), runner.learn).  The reference's own file runs unchanged
 against the package too (tests/test_script_surface.py checks what it imports and calls); this copy only adds
---iterations / --robot / --root so a short run can be asked for.
-usage: python scripts/train.py [--iterations N] [--robot mc|go1] [--root DIR]"""
+--iterations / --robot / --root so a short run can be asked for, and --terrain-tgs (the project-only key
+Cfg.sim.physx.terrain_solver_type = 1: a terrain mesh then solves contacts with the presets' TGS, as the reference's
+PhysX does, instead of this project's default PGS there; no effect on the plane).
+usage: python scripts/train.py [--iterations N] [--robot mc|go1] [--root DIR] [--terrain-tgs]"""
 import argparse
 import os
 import sys
@@ -12,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "rapid-locomotion-rl_amd"))
 
 
-def train_mc(headless=True, iterations=4000, robot="go1"):
+def train_mc(headless=True, iterations=4000, robot="go1", terrain_tgs=False):
     import isaacgym
     assert isaacgym
     import torch  # noqa: F401
@@ -28,6 +30,8 @@ def train_mc(headless=True, iterations=4000, robot="go1"):
     from ml_logger import logger
 
     (config_mini_cheetah if robot == "mc" else config_go1)(Cfg)  # (the reference's file: config_go1)
+    if terrain_tgs:
+        Cfg.sim.physx.terrain_solver_type = 1
     env = VelocityTrackingEasyEnv(sim_device="cuda:0", headless=headless, cfg=Cfg)
     logger.log_params(AC_Args=vars(AC_Args), PPO_Args=vars(PPO_Args), RunnerArgs=vars(RunnerArgs), Cfg=vars(Cfg))
     env = HistoryWrapper(env)
@@ -43,6 +47,8 @@ if __name__ == "__main__":
     ap.add_argument("--iterations", type=int, default=4000)
     ap.add_argument("--robot", default="go1", choices=["mc", "go1"])
     ap.add_argument("--root", default=None, help="run root (default: <package>/runs, as MINI_GYM_ROOT_DIR/runs)")
+    ap.add_argument("--terrain-tgs", action="store_true",
+                    help="on a terrain mesh follow Cfg.sim.physx.solver_type (TGS in the presets) instead of PGS")
     a = ap.parse_args()
     from ml_logger import logger
     from mini_gym import MINI_GYM_ROOT_DIR
@@ -57,4 +63,4 @@ if __name__ == "__main__":
                 - yKey: train/episode/command_area/mean
                   xKey: iterations
                 """, filename=".charts.yml", dedent=True)
-    train_mc(headless=True, iterations=a.iterations, robot=a.robot)
+    train_mc(headless=True, iterations=a.iterations, robot=a.robot, terrain_tgs=a.terrain_tgs)

@@ -8,7 +8,10 @@ adaptation module on the history + actor) tracks constant forward commands (scri
 line: wall time, iterations/s, the tracking rewards early vs late, the command area the curriculum reached, and
 the measured forward velocity per command.
 
-  python scripts/train_eval.py [--iterations 1500] [--out DIR]
+  python scripts/train_eval.py [--iterations 1500] [--out DIR] [--terrain-tgs]
+
+--terrain-tgs sets Cfg.sim.physx.terrain_solver_type = 1 (TGS on a terrain mesh; the Mini Cheetah preset's plane is
+not affected by it).
 """
 import argparse
 import json
@@ -34,10 +37,14 @@ def main():
     ap.add_argument("--iterations", type=int, default=1500)
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--terrain-tgs", action="store_true",
+                    help="on a terrain mesh follow Cfg.sim.physx.solver_type (TGS in the presets) instead of PGS")
     a = ap.parse_args()
     cfg = lcfg.make_cfg()
     lcfg.config_mini_cheetah(cfg)
     cfg.env.num_envs = a.envs
+    if a.terrain_tgs:
+        cfg.sim.physx.terrain_solver_type = 1
     R.RunnerArgs.save_interval = 0
     R.RunnerArgs.log_freq = 50
     env = HistoryWrapper(LeggedRobotEnv("cuda:0", cfg=cfg, seed=11, legacy_fork=False))
