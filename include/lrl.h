@@ -224,6 +224,23 @@ typedef struct lrl_env_params {
   int32_t observe_only_ang_vel, observe_only_lin_vel, observe_yaw, global_reference;
 } lrl_env_params;
 
+/* The eval group's own values of what the reference runs under _call_train_eval with the group's cfg
+ * (legged_robot.py:456-469: _randomize_dof_props :544-560 at reset and every rand_interval, _push_robots :757-766,
+ * _teleport_robots :768-791).  They travel beside lrl_env_params (lrl_sim_set_eval_group), not inside it: the size
+ * of lrl_env_params is unchanged.  Each field means what the field of the same name in lrl_env_params means for the
+ * train group (dr_span: float32 of the double hi - lo of motor_strength_range / kp_range / kd_range).  push_interval
+ * may be 0 when push_robots is 0.  rand_interval stays one value (the reference reads self.cfg's for every env, :591)
+ * and teleport_x_offset_eval stays in lrl_env_params. */
+typedef struct lrl_group_params {
+  int32_t randomize_motor_strength, randomize_kp, randomize_kd;
+  float motor_strength_range[2], kp_range[2], kd_range[2], dr_span[3];
+  int32_t push_robots, push_interval;
+  float push_lo, push_span;
+  int32_t teleport;
+  float teleport_thresh, terrain_length, terrain_width;
+  int32_t terrain_rows, terrain_cols;
+} lrl_group_params;
+
 /* ------------------------------------------------------------------------------------------
  * Sim object and its device tensors (acquire_*_tensor).
  * ------------------------------------------------------------------------------------------ */
@@ -291,9 +308,26 @@ int32_t lrl_sim_create(const lrl_model* model, const lrl_env_params* params, int
 int32_t lrl_sim_destroy(lrl_sim* sim);
 int32_t lrl_sim_tensor(lrl_sim* sim, int32_t tensor_id, lrl_tensor* out);
 
+/* Give the eval group (envs with index >= params->num_train_envs) its own lrl_group_params: from the next launch the
+ * step and reset kernels read `eval` for those envs and the lrl_env_params values for the others.  eval == NULL
+ * switches it off again (the state after lrl_sim_create): every env uses the lrl_env_params values, with
+ * teleport_x_offset_eval as the one per-group field, and every output is what it was without this call.  Validated as
+ * lrl_sim_create validates the train values (push_robots needs push_interval >= 1).  Waits for the device.  The
+ * group boundary is params->num_train_envs as given to lrl_sim_create: a caller that left it 0 puts every env into the
+ * eval group (lrl/params.py's default is 2^30: no env). */
+int32_t lrl_sim_set_eval_group(lrl_sim* sim, const lrl_group_params* eval);
+
 /* Initialise the per-env domain randomisation draws (legged_robot.py:519-542, 544-560) */
 int32_t lrl_sim_randomize(lrl_sim* sim, const float* friction_range, const float* restitution_range,
                           const float* payload_range, const float* com_range, uint32_t which, void* stream);
+/* The same draw for the envs [first_env, first_env + num_envs) only (a train / eval group with its own cfg's switches
+ * and ranges, _randomize_rigid_body_props under _call_train_eval :1231): the Philox keys are lrl_sim_randomize's
+ * (global env id, counter 0), so an env draws the same uniforms whichever call covers it.  `which`: bit 0 payload,
+ * 1 COM displacement, 2 friction, 3 restitution; the others keep their values.  The range must lie inside
+ * [0, num_envs of the sim]; an empty range launches nothing. */
+int32_t lrl_sim_randomize_envs(lrl_sim* sim, int32_t first_env, int32_t num_envs, const float* friction_range,
+                               const float* restitution_range, const float* payload_range, const float* com_range,
+                               uint32_t which, void* stream);
 
 /* One policy step for all envs: the fused LeggedRobot.step hot path. `actions` [N,12] f32 device. */
 int32_t lrl_sim_step(lrl_sim* sim, const float* actions, uint32_t flags, void* stream);
@@ -314,7 +348,8 @@ int32_t lrl_sim_self_contact_stats(lrl_sim* sim, int32_t enable, uint64_t* out);
 /* Injected uniforms for parity tests: noise_u [N,num_obs], dr_u [N] (NaN = no redraw). */
 int32_t lrl_sim_inject_uniforms(lrl_sim* sim, const float* noise_u, const float* dr_u);
 /* Injected push uniforms for parity tests: u [N,2] f32 device, row e = env e's (x, y) draw of _push_robots when it is
- * pushed in the step (legged_robot.py:763-764); required with LRL_STEP_INJECT_UNIFORM when push_robots is on. */
+ * pushed in the step (legged_robot.py:763-764); required with LRL_STEP_INJECT_UNIFORM when push_robots is on in either
+ * group (push_robots, or lrl_sim_set_eval_group's eval->push_robots). */
 int32_t lrl_sim_inject_push_uniforms(lrl_sim* sim, const float* u);
 
 int32_t lrl_sim_reset_idx(lrl_sim* sim, const int32_t* env_ids, int32_t n, void* stream);

@@ -50,16 +50,21 @@ __global__ void reset_kernel(const KParams* __restrict__ K, KState S, const int3
   }
   // torch.rand(k) * (max - min) + min: two float32 roundings, the span rounded once from the python floats
   auto draw = [](float uu, float span, float lo) { return uu * span + lo; };
-  if (P.randomize_motor_strength) {
-    float v = draw(u[0], P.dr_span[0], P.motor_strength_range[0]);
+  // the env's group (lrl_sim_set_eval_group): an id list may mix both, so both groups' values are read (uniform
+  // loads; by value, not `ge ? G.x : P.x`, which would select an address per thread) and selected per thread
+  const lrl_group_params& G = K->ev;
+  const bool ge = K->eval_group != 0 && e >= P.num_train_envs;
+  auto grp = [ge](auto train, auto eval) { return ge ? eval : train; };
+  if (grp(P.randomize_motor_strength, G.randomize_motor_strength)) {
+    float v = draw(u[0], grp(P.dr_span[0], G.dr_span[0]), grp(P.motor_strength_range[0], G.motor_strength_range[0]));
     for (int j = 0; j < 12; ++j) S.motor_strength[j * N + e] = v;
   }
-  if (P.randomize_kp) {
-    float v = draw(u[1], P.dr_span[1], P.kp_range[0]);
+  if (grp(P.randomize_kp, G.randomize_kp)) {
+    float v = draw(u[1], grp(P.dr_span[1], G.dr_span[1]), grp(P.kp_range[0], G.kp_range[0]));
     for (int j = 0; j < 12; ++j) S.kp[j * N + e] = v;
   }
-  if (P.randomize_kd) {
-    float v = draw(u[2], P.dr_span[2], P.kd_range[0]);
+  if (grp(P.randomize_kd, G.randomize_kd)) {
+    float v = draw(u[2], grp(P.dr_span[2], G.dr_span[2]), grp(P.kd_range[0], G.kd_range[0]));
     for (int j = 0; j < 12; ++j) S.kd[j * N + e] = v;
   }
   for (int j = 0; j < 12; ++j) {
@@ -306,11 +311,12 @@ __global__ void shift_history_kernel(KState S, int NO, int H, int append) {
   for (int k = threadIdx.x; k < W; k += blockDim.x) h[k] = row[k];
 }
 
-// _randomize_rigid_body_props (legged_robot.py:519-542) for all envs
-__global__ void randomize_kernel(KState S, float f0, float f1, float r0, float r1, float p0, float p1, float c0,
-                                 float c1, uint32_t which) {
-  int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= S.stride) return;
+// _randomize_rigid_body_props (legged_robot.py:519-542) for the envs [first, end): all of them (lrl_sim_randomize: 0 to
+// the padded count) or one train / eval group (lrl_sim_randomize_envs); the draws' keys are the global env ids either way
+__global__ void randomize_kernel(KState S, int32_t first, int32_t end, float f0, float f1, float r0, float r1, float p0,
+                                 float p1, float c0, float c1, uint32_t which) {
+  int e = first + blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= end || e >= S.stride) return;
   const int N = S.stride;
   uint64_t genv = (uint64_t)(S.env_offset + e);
   lrl_u32x4 a = lrl_philox((uint32_t)genv, 0u, (LRL_RNG_INIT << 16), 0, S.seed);
@@ -545,10 +551,11 @@ hipError_t lrl_launch_shift_history(const KState* S, int NO, int H, int append, 
   hipLaunchKernelGGL(lrl::shift_history_kernel, dim3(S->n), dim3(128), H * sizeof(float), st, *S, NO, H, append);
   return hipGetLastError();
 }
-hipError_t lrl_launch_randomize(const KState* S, const float* fr, const float* rr, const float* pr, const float* cr,
-                                uint32_t which, hipStream_t st) {
-  hipLaunchKernelGGL(lrl::randomize_kernel, dim3((S->stride + 255) / 256), dim3(256), 0, st, *S, fr[0], fr[1], rr[0],
-                     rr[1], pr[0], pr[1], cr[0], cr[1], which);
+hipError_t lrl_launch_randomize(const KState* S, int32_t first, int32_t end, const float* fr, const float* rr,
+                                const float* pr, const float* cr, uint32_t which, hipStream_t st) {
+  if (end <= first) return hipSuccess;
+  hipLaunchKernelGGL(lrl::randomize_kernel, dim3((end - first + 255) / 256), dim3(256), 0, st, *S, first, end, fr[0],
+                     fr[1], rr[0], rr[1], pr[0], pr[1], cr[0], cr[1], which);
   return hipGetLastError();
 }
 }

@@ -53,8 +53,8 @@ hipError_t lrl_launch_extras_snapshot(const KParams*, const KState*, const int32
                                       hipStream_t);
 hipError_t lrl_launch_shift_history(const KState*, int, int, int, hipStream_t);
 hipError_t lrl_launch_garbage(uint32_t mode, uint32_t pat, hipStream_t st);
-hipError_t lrl_launch_randomize(const KState*, const float*, const float*, const float*, const float*, uint32_t,
-                                hipStream_t);
+hipError_t lrl_launch_randomize(const KState*, int32_t, int32_t, const float*, const float*, const float*, const float*,
+                                uint32_t, hipStream_t);
 hipError_t lrl_launch_render(const KParams*, const KState*, const KRender*, const lrl_camera*, int32_t, uint8_t*, float*,
                              int32_t*, const int32_t*, hipStream_t);
 hipError_t lrl_launch_record_state(const KState*, int32_t, int32_t, int32_t*, hipStream_t);
@@ -590,7 +590,8 @@ int32_t lrl_sim_step(lrl_sim* s, const float* actions, uint32_t flags, void* str
   if (!s || !actions) return fail(LRL_E_INVALID, "null argument");
   if ((flags & LRL_STEP_INJECT_UNIFORM) && (!s->S.inj_noise || !s->S.inj_dr))
     return fail(LRL_E_INVALID, "injected uniforms not set");
-  if ((flags & LRL_STEP_INJECT_UNIFORM) && s->hk.p.push_robots && !s->S.inj_push)
+  if ((flags & LRL_STEP_INJECT_UNIFORM) && (s->hk.p.push_robots || (s->hk.eval_group && s->hk.ev.push_robots)) &&
+      !s->S.inj_push)
     return fail(LRL_E_INVALID, "push_robots on but injected push uniforms not set");
   if (s->hk.p.terrain_mesh && !s->hk.terr_vtx) return fail(LRL_E_INVALID, "terrain_mesh set but no lrl_sim_set_terrain");
   s->step_counter += 1;  // common_step_counter (legged_robot.py:153)
@@ -609,7 +610,8 @@ int32_t lrl_sim_step(lrl_sim* s, const float* actions, uint32_t flags, void* str
     tp = &s->ev[s->ev_used++];
     HIPCHECK(hipEventRecord(tp->first, (hipStream_t)stream));
   }
-  HIPCHECK(lrl_launch_env_step(s->dk, &s->S, s->lds_bytes, actions, flags, s->step_counter, s->hk.p.terrain_mesh, s->mesh_tgs,
+  const uint32_t kflags = (flags & ~LRL_STEP_KGROUP) | (s->hk.eval_group ? LRL_STEP_KGROUP : 0u);
+  HIPCHECK(lrl_launch_env_step(s->dk, &s->S, s->lds_bytes, actions, kflags, s->step_counter, s->hk.p.terrain_mesh, s->mesh_tgs,
                                (hipStream_t)stream));
   if (tp) HIPCHECK(hipEventRecord(tp->second, (hipStream_t)stream));
   return 0;
@@ -864,7 +866,30 @@ int32_t lrl_sim_shift_history(lrl_sim* s, void* stream) {
 int32_t lrl_sim_randomize(lrl_sim* s, const float* fr, const float* rr, const float* pr, const float* cr,
                           uint32_t which, void* stream) {
   if (!s || !fr || !rr || !pr || !cr) return fail(LRL_E_INVALID, "null argument");
-  HIPCHECK(lrl_launch_randomize(&s->S, fr, rr, pr, cr, which, (hipStream_t)stream));
+  HIPCHECK(lrl_launch_randomize(&s->S, 0, s->S.stride, fr, rr, pr, cr, which, (hipStream_t)stream));
+  return 0;
+}
+
+int32_t lrl_sim_randomize_envs(lrl_sim* s, int32_t first_env, int32_t num_envs, const float* fr, const float* rr,
+                               const float* pr, const float* cr, uint32_t which, void* stream) {
+  if (!s || !fr || !rr || !pr || !cr) return fail(LRL_E_INVALID, "null argument");
+  if (first_env < 0 || num_envs < 0 || first_env > s->S.n || num_envs > s->S.n - first_env)
+    return fail(LRL_E_INVALID, "env range [%d, %d + %d) outside the sim's %d envs", first_env, first_env, num_envs,
+                s->S.n);
+  HIPCHECK(lrl_launch_randomize(&s->S, first_env, first_env + num_envs, fr, rr, pr, cr, which, (hipStream_t)stream));
+  return 0;
+}
+
+int32_t lrl_sim_set_eval_group(lrl_sim* s, const lrl_group_params* g) {
+  if (!s) return fail(LRL_E_INVALID, "null sim");
+  if (g && g->push_robots && g->push_interval < 1)
+    return fail(LRL_E_INVALID, "eval group: push_robots with push_interval < 1");
+  HIPCHECK(hipSetDevice(s->device));
+  HIPCHECK(hipDeviceSynchronize());  // no launch in flight reads the parameter block replaced below
+  s->hk.eval_group = g ? 1 : 0;
+  if (g) s->hk.ev = *g;
+  else memset(&s->hk.ev, 0, sizeof(s->hk.ev));
+  HIPCHECK(hipMemcpy(s->dk, &s->hk, sizeof(KParams), hipMemcpyHostToDevice));
   return 0;
 }
 

@@ -2525,14 +2525,31 @@ __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restri
   const int NO = P.num_obs;
   float* otile = lds;                    // [ENVS][NO]
   float* ptile = lds + ENVS * NO;        // [ENVS][18]
+  // The env's group (lrl_sim_set_eval_group; _call_train_eval, legged_robot.py:456-469).  Without an eval block the
+  // three per-group blocks below take p's values and nothing else is read: grp_on is a bit of the launch's flags
+  // (LRL_STEP_KGROUP, set by lrl_sim_step), so the default path pays one wave-uniform branch per block and no load.
+  // With a block, a wave may hold envs of both groups, so the group is a lane property: both groups' values are
+  // wave-uniform scalar loads, selected per lane.  grp takes the two by value: `ge ? G.x : P.x` on the fields themselves
+  // selects an address per lane and turns the read into a vector load.
+  const lrl_group_params& G = K->ev;
+  const bool grp_on = flags & LRL_STEP_KGROUP;
+  const bool ge = e >= P.num_train_envs;  // (read under grp_on only)
+  auto grp = [ge](auto train, auto eval) { return ge ? eval : train; };
   // _teleport_robots (legged_robot.py:768-791), in every lane of the env (the height scan below needs it)
-  if (P.teleport) {
-    float th = P.teleport_thresh;
-    float xo = (float)(int)(e < P.num_train_envs ? P.teleport_x_offset : P.teleport_x_offset_eval);
-    if (st.pos[0] < th + xo) st.pos[0] += P.terrain_length * (float)(P.terrain_rows - 1);
-    if (st.pos[0] > P.terrain_length * (float)P.terrain_rows - th + xo) st.pos[0] -= P.terrain_length * (float)(P.terrain_rows - 1);
-    if (st.pos[1] < th) st.pos[1] += P.terrain_width * (float)(P.terrain_cols - 1);
-    if (st.pos[1] > P.terrain_width * (float)P.terrain_cols - th) st.pos[1] -= P.terrain_width * (float)(P.terrain_cols - 1);
+  {
+    int on = P.teleport, tr = P.terrain_rows, tc = P.terrain_cols;
+    float th = P.teleport_thresh, tl = P.terrain_length, tw = P.terrain_width;
+    if (grp_on) {
+      on = grp(on, G.teleport), tr = grp(tr, G.terrain_rows), tc = grp(tc, G.terrain_cols);
+      th = grp(th, G.teleport_thresh), tl = grp(tl, G.terrain_length), tw = grp(tw, G.terrain_width);
+    }
+    if (on) {
+      float xo = (float)(int)(e < P.num_train_envs ? P.teleport_x_offset : P.teleport_x_offset_eval);
+      if (st.pos[0] < th + xo) st.pos[0] += tl * (float)(tr - 1);
+      if (st.pos[0] > tl * (float)tr - th + xo) st.pos[0] -= tl * (float)(tr - 1);
+      if (st.pos[1] < th) st.pos[1] += tw * (float)(tc - 1);
+      if (st.pos[1] > tw * (float)tc - th) st.pos[1] -= tw * (float)(tc - 1);
+    }
   }
   // _get_heights (legged_robot.py:1469-1503) after the teleport (:575-585): the scan points spread over the
   // env's 4 lanes, written to measured_heights and to the height entries of the obs row (:386-389)
@@ -2558,7 +2575,14 @@ __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restri
   const bool inject = flags & LRL_STEP_INJECT_UNIFORM;
   // _push_robots (legged_robot.py:757-766): after the base-frame velocities above, before the rewards; the pushed
   // root velocity is what root_states, the next step's physics and last_root_vel see
-  if (P.push_robots && eplen % P.push_interval == 0) {
+  int push_on = P.push_robots, push_iv = P.push_interval;
+  float pspan = P.push_span, plo = P.push_lo;
+  if (grp_on) {  // (a group that does not push may carry push_interval 0: no modulo by it)
+    push_on = grp(push_on, G.push_robots), push_iv = grp(push_iv, G.push_interval);
+    push_iv = push_iv > 0 ? push_iv : 1;
+    pspan = grp(pspan, G.push_span), plo = grp(plo, G.push_lo);
+  }
+  if (push_on && eplen % push_iv == 0) {
     float u0, u1;
     if (inject) {
       u0 = valid ? S.inj_push[(size_t)e * 2] : 0.5f;
@@ -2569,8 +2593,8 @@ __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restri
       u0 = lrl_u01(r.v[0]);
       u1 = lrl_u01(r.v[1]);
     }
-    st.V[0] = P.push_span * u0 + P.push_lo;  // (upper - lower) * torch.rand + lower
-    st.V[1] = P.push_span * u1 + P.push_lo;
+    st.V[0] = pspan * u0 + plo;  // (upper - lower) * torch.rand + lower
+    st.V[1] = pspan * u1 + plo;
   }
   // global_reference's tracking_lin_vel error (:1580-1581: against root_states[:, 7:9], the world velocity after the
   // push), taken here where the velocity is in registers: one value carried to the reward loop instead of two
@@ -2653,6 +2677,15 @@ __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restri
 #pragma unroll
   for (int j = 0; j < 12; ++j) ms_e[j] = S.motor_strength[j * N + e];
   if (P.rand_interval > 0 && eplen % P.rand_interval == 0) {
+    int on_ms = P.randomize_motor_strength, on_kp = P.randomize_kp, on_kd = P.randomize_kd;
+    float span_ms = P.dr_span[0], span_kp = P.dr_span[1], span_kd = P.dr_span[2];
+    float lo_ms = P.motor_strength_range[0], lo_kp = P.kp_range[0], lo_kd = P.kd_range[0];
+    if (grp_on) {
+      on_ms = grp(on_ms, G.randomize_motor_strength), on_kp = grp(on_kp, G.randomize_kp);
+      on_kd = grp(on_kd, G.randomize_kd);
+      span_ms = grp(span_ms, G.dr_span[0]), span_kp = grp(span_kp, G.dr_span[1]), span_kd = grp(span_kd, G.dr_span[2]);
+      lo_ms = grp(lo_ms, G.motor_strength_range[0]), lo_kp = grp(lo_kp, G.kp_range[0]), lo_kd = grp(lo_kd, G.kd_range[0]);
+    }
     int k = 0;
     lrl_u32x4 r = lrl_philox((uint32_t)genv, (uint32_t)step_counter, (LRL_RNG_DR << 16) ^ (uint32_t)(step_counter >> 32), 0,
                              S.seed);
@@ -2660,26 +2693,26 @@ __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restri
     // array in scratch)
     const uint32_t w0 = r.v[0], w1 = r.v[1], w2 = r.v[2];
     auto word = [&](int i) { return i == 0 ? w0 : (i == 1 ? w1 : w2); };
-    if (P.randomize_motor_strength) {
+    if (on_ms) {
       float u = inject ? (valid ? S.inj_dr[e] : 0.5f) : lrl_u01(word(k));
       k++;
       // torch.rand * (max - min) + min: two float32 roundings, the span rounded from the python-float difference
-      float v = u * P.dr_span[0] + P.motor_strength_range[0];
+      float v = u * span_ms + lo_ms;
 #pragma unroll
       for (int j = 0; j < 12; ++j) {
         ms_e[j] = v;
         S.motor_strength[j * N + e] = v;
       }
     }
-    if (P.randomize_kp) {
+    if (on_kp) {
       float u = lrl_u01(word(k++));
-      float v = u * P.dr_span[1] + P.kp_range[0];
+      float v = u * span_kp + lo_kp;
 #pragma unroll
       for (int j = 0; j < 12; ++j) S.kp[j * N + e] = v;
     }
-    if (P.randomize_kd) {
+    if (on_kd) {
       float u = lrl_u01(word(k++));
-      float v = u * P.dr_span[2] + P.kd_range[0];
+      float v = u * span_kd + lo_kd;
 #pragma unroll
       for (int j = 0; j < 12; ++j) S.kd[j * N + e] = v;
     }

@@ -90,7 +90,14 @@ struct KParams {
   // lrl_sim_self_contact_stats: null (off), or 4 device counters [env-sub-steps with a self-contact, pairs in contact,
   // env-sub-steps with more pairs than slots, pairs without a slot]
   uint32_t* self_stats;
+  // lrl_sim_set_eval_group: 0 = every env reads p's domain-randomisation / push / teleport values; 1 = the envs with
+  // index >= p.num_train_envs read ev's (the step kernel's three builds and reset_kernel select per lane)
+  int32_t eval_group;
+  lrl_group_params ev;
 };
+// Internal bit of the env step kernel's flags: the sim has an eval block (KParams::eval_group).  lrl_sim_step sets it
+// from the host copy, so that the kernel's default path tests a launch argument and reads nothing of the block.
+#define LRL_STEP_KGROUP 0x80000000u
 
 // lrl_sim_render's view of the model (lrl_render.hip), built by lrl_sim_create and passed to the kernel by value
 struct KRender {

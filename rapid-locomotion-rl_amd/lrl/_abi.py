@@ -45,6 +45,18 @@ class LrlModel(C.Structure):
     ]
 
 
+class LrlGroupParams(C.Structure):
+    """lrl_group_params (lrl_sim_set_eval_group): the eval group's own domain-randomisation, push and teleport values;
+    every field has the name and type of its LrlEnvParams counterpart."""
+    _fields_ = [
+        ("randomize_motor_strength", i32), ("randomize_kp", i32), ("randomize_kd", i32),
+        ("motor_strength_range", f32 * 2), ("kp_range", f32 * 2), ("kd_range", f32 * 2), ("dr_span", f32 * 3),
+        ("push_robots", i32), ("push_interval", i32), ("push_lo", f32), ("push_span", f32),
+        ("teleport", i32), ("teleport_thresh", f32), ("terrain_length", f32), ("terrain_width", f32),
+        ("terrain_rows", i32), ("terrain_cols", i32),
+    ]
+
+
 class LrlEnvParams(C.Structure):
     _fields_ = [
         ("sim_dt", f32), ("decimation", i32), ("dt", f32), ("gravity", f32 * 3),
@@ -216,6 +228,7 @@ def lib():
         for name in ["lrl_sim_create", "lrl_sim_destroy", "lrl_sim_tensor", "lrl_sim_step", "lrl_sim_reset_idx",
                      "lrl_sim_set_root_state_indexed", "lrl_sim_set_dof_state_indexed", "lrl_sim_inject_uniforms",
                      "lrl_sim_refresh_rigid_body_state", "lrl_sim_shift_history", "lrl_sim_randomize", "lrl_gae",
+                     "lrl_sim_randomize_envs", "lrl_sim_set_eval_group",
                      "lrl_ppo_act", "lrl_abi_version", "lrl_device_count", "lrl_gae_partial", "lrl_adv_normalize",
                      "lrl_sim_reset_idx_ex", "lrl_sim_observe_idx", "lrl_sim_set_step_counter", "lrl_ppo_forward_backward",
                      "lrl_ppo_optimizer_step", "lrl_ppo_adaptation_forward_backward", "lrl_ppo_adaptation_step",

@@ -164,6 +164,37 @@ def _apply(cfg, updates):
         setattr(node, leaf, copy.deepcopy(value))
 
 
+def _register_paths(sec, path=""):
+    if path:
+        _PATHS[id(sec)] = (weakref.ref(sec), path)
+    for k, v in vars(sec).items():
+        if isinstance(v, Section):
+            _register_paths(v, f"{path}.{k}" if path else k)
+
+
+def eval_variant(cfg, num_envs, sets=()):
+    """An eval cfg for ``LeggedRobotEnv(cfg=cfg, eval_cfg=...)``: an independent copy of ``cfg`` with ``num_envs`` envs
+    and the assignments ``sets`` applied, each a string ``PATH=VALUE`` (scripts/train.py --eval-set) whose value is a
+    python literal: ``domain_rand.friction_range=[0.05,0.06]``, ``domain_rand.push_robots=True``.  PATH must name an
+    existing field (a typo would otherwise evaluate on the training distribution without a word)."""
+    import ast
+    ecfg = copy.deepcopy(cfg)
+    _register_paths(ecfg)
+    ecfg.env.num_envs = int(num_envs)
+    for item in sets:
+        path, sep, text = str(item).partition("=")
+        if not sep:
+            raise ValueError(f"--eval-set wants PATH=VALUE, got {item!r}")
+        node = ecfg
+        *parents, leaf = path.strip().split(".")
+        for p in parents:
+            node = getattr(node, p)
+        if not hasattr(node, leaf):
+            raise AttributeError(f"cfg has no field {path.strip()!r}")
+        setattr(node, leaf, ast.literal_eval(text.strip()))
+    return ecfg
+
+
 _COMMON_PRESET = {
     "control.control_type": "P", "control.stiffness": {"joint": 20.0}, "control.damping": {"joint": 0.5},
     "control.action_scale": 0.25, "control.hip_scale_reduction": 0.5, "control.decimation": 4,

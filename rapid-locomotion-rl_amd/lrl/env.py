@@ -241,23 +241,17 @@ class LeggedRobotEnv:
             terrain_mesh = self._create_terrain()
         self._P = lparams.build_params(cfg, self.robot, auto_reset=not self.legacy_fork,
                                        solver_iterations=solver_iterations, terrain_mesh=terrain_mesh)
+        self._G = None  # the eval group's lrl_group_params, when its cfg differs in them
         if eval_cfg is not None:
-            # one kernel parameter block serves both groups: the eval cfg may differ from the train cfg only in
-            # what the host applies per group (command ranges / curriculum, reset logging)
+            # The eval cfg may differ from the train cfg in what the host applies per group (command ranges /
+            # curriculum, reset logging, init ranges, rigid-body DR at creation) and in what the reference runs
+            # under _call_train_eval with the group's cfg (lparams.GROUP_FIELDS): those become the eval group's
+            # lrl_group_params.  Any other kernel parameter is shared, and a difference in one is refused.
             Pe = lparams.build_params(eval_cfg, self.robot, auto_reset=not self.legacy_fork,
                                       solver_iterations=solver_iterations, terrain_mesh=terrain_mesh)
-            # the eval tiles' teleport x offset is the one per-group kernel parameter
             self._P.num_train_envs = self.num_train_envs
             self._P.teleport_x_offset_eval = Pe.teleport_x_offset
-            Pe.teleport_x_offset, Pe.teleport_x_offset_eval = self._P.teleport_x_offset, Pe.teleport_x_offset
-            Pe.num_train_envs = self._P.num_train_envs
-            def differs(f):
-                a, b = getattr(self._P, f), getattr(Pe, f)
-                return bytes(a) != bytes(b) if isinstance(a, C.Array) else a != b
-            diff = [f for f, _ in type(self._P)._fields_ if differs(f)]
-            if diff:
-                raise NotImplementedError(f"eval_cfg differs from cfg in per-step kernel parameters {diff}; "
-                                          "only host-side (command / curriculum) differences are supported")
+            self._G = lparams.eval_group_params(self._P, Pe)
         self._M = lparams.build_model(self.robot)
         self.sim_params = Section(dt=lparams.sim_dt(cfg))
         self.dt = cfg.control.decimation * self.sim_params.dt
@@ -280,6 +274,8 @@ class LeggedRobotEnv:
                                     C.c_int64(env_offset), C.c_uint64(self.seed), C.c_int32(dev_index),
                                     C.byref(self._sim)))
         self._dev_index = dev_index
+        if self._G is not None:
+            _abi.check(L.lrl_sim_set_eval_group(self._sim, C.byref(self._G)))
         if terrain_mesh:  # gym.add_triangle_mesh / add_heightfield (legged_robot.py:1122-1160)
             t = self.terrain
             if cfg.terrain.mesh_type == "trimesh":
@@ -365,13 +361,22 @@ class LeggedRobotEnv:
         self.all_root_states[:, 0:3] = self.env_origins
         self.all_root_states[:, 3:7] = torch.tensor([0.0, 0.0, 0.0, 1.0], device=self.device)
         self.all_root_states[:, 7:13] = 0.0
-        dr = cfg.domain_rand
-        which = (int(dr.randomize_base_mass) | (int(dr.randomize_com_displacement) << 1) |
-                 (int(dr.randomize_friction) << 2) | (int(dr.randomize_restitution) << 3))
         arr = lambda r: (C.c_float * 2)(*[float(x) for x in r])
-        _abi.check(L.lrl_sim_randomize(self._sim, arr(dr.friction_range), arr(dr.restitution_range),
-                                       arr(dr.added_mass_range), arr(dr.com_displacement_range), C.c_uint32(which),
-                                       self._stream()))
+
+        def rigid_body_draw(dr, first=None, count=None):
+            which = (int(dr.randomize_base_mass) | (int(dr.randomize_com_displacement) << 1) |
+                     (int(dr.randomize_friction) << 2) | (int(dr.randomize_restitution) << 3))
+            ranges = (arr(dr.friction_range), arr(dr.restitution_range), arr(dr.added_mass_range),
+                      arr(dr.com_displacement_range), C.c_uint32(which), self._stream())
+            if first is None:
+                _abi.check(L.lrl_sim_randomize(self._sim, *ranges))
+            else:
+                _abi.check(L.lrl_sim_randomize_envs(self._sim, C.c_int32(first), C.c_int32(count), *ranges))
+        if eval_cfg is None:
+            rigid_body_draw(cfg.domain_rand)
+        else:  # each group with its own cfg's switches and ranges (_call_train_eval, :1231); keys are global env ids
+            rigid_body_draw(cfg.domain_rand, 0, self.num_train_envs)
+            rigid_body_draw(eval_cfg.domain_rand, self.num_train_envs, self.num_eval_envs)
         if initial_dynamics_dict is not None:
             for k, v in initial_dynamics_dict.items():
                 if hasattr(self, k) and isinstance(getattr(self, k), torch.Tensor):

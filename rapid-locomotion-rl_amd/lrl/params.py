@@ -117,6 +117,46 @@ def terrain_solver(cfg, override=None):
     return int(getattr(cfg.sim.physx, "terrain_solver_type", 0) if override is None else override)
 
 
+# what the reference runs under _call_train_eval with the group's own cfg (legged_robot.py:456-469:
+# _randomize_dof_props, _push_robots, _teleport_robots): the fields of lrl_group_params, named as in lrl_env_params
+GROUP_FIELDS = tuple(f for f, _ in _abi.LrlGroupParams._fields_)
+# per-group already (the eval tiles' x offset), or set by the env for both blocks
+_GROUP_NEUTRAL = ("teleport_x_offset", "teleport_x_offset_eval", "num_train_envs")
+
+
+def _field_bytes(S, f):
+    v = getattr(S, f)
+    return bytes(v) if isinstance(v, _abi.C.Array) else v
+
+
+def group_params(P):
+    """The lrl_group_params of a built parameter block: its own values of the per-group fields."""
+    G = _abi.LrlGroupParams()
+    for f in GROUP_FIELDS:
+        v = getattr(P, f)
+        setattr(G, f, type(v)(*v) if isinstance(v, _abi.C.Array) else v)
+    return G
+
+
+def eval_group_params(P, Pe):
+    """The eval group's parameters, given the train cfg's block P and the eval cfg's block Pe (build_params of each).
+
+    None when the two agree in every kernel parameter (one block serves both groups: lrl_sim_set_eval_group is not
+    called); the eval group's lrl_group_params when they differ in per-group fields only (GROUP_FIELDS: motor
+    strength / Kp / Kd switches and ranges, the push switch, interval and velocity, the teleport geometry).  A
+    difference in anything else -- control gains, rewards, observation layout, noise, solver, rand_interval: what the
+    reference reads from self.cfg for every env -- raises NotImplementedError naming those fields.  The eval tiles'
+    teleport x offset and num_train_envs are not compared: the env sets them per group itself."""
+    diff = [f for f, _ in type(P)._fields_
+            if f not in _GROUP_NEUTRAL and _field_bytes(P, f) != _field_bytes(Pe, f)]
+    other = [f for f in diff if f not in GROUP_FIELDS]
+    if other:
+        raise NotImplementedError(f"eval_cfg differs from cfg in per-step kernel parameters {other}; beside the "
+                                  "host-side (command / curriculum) differences only the fields of lrl_group_params "
+                                  "may differ")
+    return group_params(Pe) if diff else None
+
+
 def build_params(cfg, robot, auto_reset=False, solver_iterations=None, baumgarte=0.2, terrain_mesh=0,
                  joint_limits=True, joint_limit_margin=0.02, self_collisions=None, solver_type=None,
                  terrain_solver_type=None):

@@ -169,11 +169,11 @@ class Terrain:
         self.train_rows, self.train_cols, self.eval_rows, self.eval_cols = self._layout()
         self.tot_rows = len(self.train_rows) + len(self.eval_rows)
         self.tot_cols = max(len(self.train_cols), len(self.eval_cols))
-        cfg.env_length, cfg.env_width = cfg.terrain_length, cfg.terrain_width
         self.height_field_raw = np.zeros((self.tot_rows, self.tot_cols), dtype=np.int16)
         for c in (cfg, eval_cfg):
             if c is None:
                 continue
+            c.env_length, c.env_width = c.terrain_length, c.terrain_width  # (the eval cfg's too: its curriculum reads it)
             if c.curriculum:
                 self._curriculum(c)
             elif c.selected:

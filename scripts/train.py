@@ -4,8 +4,14 @@ VelocityTrackingEasyEnv, HistoryWrapper, Runner(env, device), runner.learn).  Th
 against the package too (tests/test_script_surface.py checks what it imports and calls); this copy only adds
 --iterations / --robot / --root so a short run can be asked for, and --terrain-tgs (the project-only key
 Cfg.sim.physx.terrain_solver_type = 1: a terrain mesh then solves contacts with the presets' TGS, as the reference's
-PhysX does, instead of this project's default PGS there; no effect on the plane).
-usage: python scripts/train.py [--iterations N] [--robot mc|go1] [--root DIR] [--terrain-tgs]"""
+PhysX does, instead of this project's default PGS there; no effect on the plane), and --eval-envs / --eval-set: an
+eval group of N envs after the train envs (the reference's eval_cfg), driven by the student policy and logged under
+eval/episode, whose cfg is a copy of the train cfg with every PATH=VALUE applied (VALUE a python literal).  The eval
+cfg may differ in command ranges and in domain randomisation, pushes and teleport; e.g. a narrow
+low-friction evaluation without pushes:
+  --eval-envs 512 --eval-set domain_rand.friction_range=[0.05,0.06] --eval-set domain_rand.push_robots=False
+usage: python scripts/train.py [--iterations N] [--robot mc|go1] [--root DIR] [--terrain-tgs]
+                               [--eval-envs N [--eval-set PATH=VALUE ...]]"""
 import argparse
 import os
 import sys
@@ -14,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "rapid-locomotion-rl_amd"))
 
 
-def train_mc(headless=True, iterations=4000, robot="go1", terrain_tgs=False):
+def train_mc(headless=True, iterations=4000, robot="go1", terrain_tgs=False, eval_envs=0, eval_set=()):
     import isaacgym
     assert isaacgym
     import torch  # noqa: F401
@@ -32,7 +38,11 @@ def train_mc(headless=True, iterations=4000, robot="go1", terrain_tgs=False):
     (config_mini_cheetah if robot == "mc" else config_go1)(Cfg)  # (the reference's file: config_go1)
     if terrain_tgs:
         Cfg.sim.physx.terrain_solver_type = 1
-    env = VelocityTrackingEasyEnv(sim_device="cuda:0", headless=headless, cfg=Cfg)
+    eval_cfg = None
+    if eval_envs:
+        from lrl.config import eval_variant
+        eval_cfg = eval_variant(Cfg, eval_envs, eval_set)
+    env = VelocityTrackingEasyEnv(sim_device="cuda:0", headless=headless, cfg=Cfg, eval_cfg=eval_cfg)
     logger.log_params(AC_Args=vars(AC_Args), PPO_Args=vars(PPO_Args), RunnerArgs=vars(RunnerArgs), Cfg=vars(Cfg))
     env = HistoryWrapper(env)
     runner = Runner(env, device="cuda:0")
@@ -49,7 +59,13 @@ if __name__ == "__main__":
     ap.add_argument("--root", default=None, help="run root (default: <package>/runs, as MINI_GYM_ROOT_DIR/runs)")
     ap.add_argument("--terrain-tgs", action="store_true",
                     help="on a terrain mesh follow Cfg.sim.physx.solver_type (TGS in the presets) instead of PGS")
+    ap.add_argument("--eval-envs", type=int, default=0, help="envs of an eval group after the train envs (0: none)")
+    ap.add_argument("--eval-set", action="append", default=[], metavar="PATH=VALUE",
+                    help="set a field of the eval cfg (a copy of the train cfg), e.g. "
+                         "domain_rand.friction_range=[0.05,0.06]; repeatable")
     a = ap.parse_args()
+    if a.eval_set and not a.eval_envs:
+        ap.error("--eval-set needs --eval-envs")
     from ml_logger import logger
     from mini_gym import MINI_GYM_ROOT_DIR
 
@@ -63,4 +79,5 @@ if __name__ == "__main__":
                 - yKey: train/episode/command_area/mean
                   xKey: iterations
                 """, filename=".charts.yml", dedent=True)
-    train_mc(headless=True, iterations=a.iterations, robot=a.robot, terrain_tgs=a.terrain_tgs)
+    train_mc(headless=True, iterations=a.iterations, robot=a.robot, terrain_tgs=a.terrain_tgs,
+             eval_envs=a.eval_envs, eval_set=a.eval_set)

@@ -8,10 +8,11 @@ adaptation module on the history + actor) tracks constant forward commands (scri
 line: wall time, iterations/s, the tracking rewards early vs late, the command area the curriculum reached, and
 the measured forward velocity per command.
 
-  python scripts/train_eval.py [--iterations 1500] [--out DIR] [--terrain-tgs]
+  python scripts/train_eval.py [--iterations 1500] [--out DIR] [--terrain-tgs] [--eval-envs N [--eval-set PATH=VALUE ...]]
 
 --terrain-tgs sets Cfg.sim.physx.terrain_solver_type = 1 (TGS on a terrain mesh; the Mini Cheetah preset's plane is
-not affected by it).
+not affected by it).  --eval-envs N adds an eval group of N envs whose cfg is a copy of the train cfg with every
+--eval-set PATH=VALUE applied (as scripts/train.py); its episode means are printed as eval_* beside the train ones.
 """
 import argparse
 import json
@@ -39,7 +40,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--terrain-tgs", action="store_true",
                     help="on a terrain mesh follow Cfg.sim.physx.solver_type (TGS in the presets) instead of PGS")
+    ap.add_argument("--eval-envs", type=int, default=0, help="envs of an eval group after the train envs (0: none)")
+    ap.add_argument("--eval-set", action="append", default=[], metavar="PATH=VALUE",
+                    help="set a field of the eval cfg (a copy of the train cfg); repeatable")
     a = ap.parse_args()
+    if a.eval_set and not a.eval_envs:
+        ap.error("--eval-set needs --eval-envs")
     cfg = lcfg.make_cfg()
     lcfg.config_mini_cheetah(cfg)
     cfg.env.num_envs = a.envs
@@ -47,7 +53,8 @@ def main():
         cfg.sim.physx.terrain_solver_type = 1
     R.RunnerArgs.save_interval = 0
     R.RunnerArgs.log_freq = 50
-    env = HistoryWrapper(LeggedRobotEnv("cuda:0", cfg=cfg, seed=11, legacy_fork=False))
+    eval_cfg = lcfg.eval_variant(cfg, a.eval_envs, a.eval_set) if a.eval_envs else None
+    env = HistoryWrapper(LeggedRobotEnv("cuda:0", cfg=cfg, eval_cfg=eval_cfg, seed=11, legacy_fork=False))
     runner = R.Runner(env, device="cuda:0", seed=11)
     t0 = time.time()
     chunk, hist = 50, []
@@ -62,6 +69,9 @@ def main():
             v = ep.get(key)
             if v is not None:
                 row[key] = round(float(v), 5)
+        for key, v in env.env.extras.get("eval/episode", {}).items() if eval_cfg is not None else ():
+            if key in ("rew_total", "rew_tracking_lin_vel", "rew_tracking_ang_vel"):
+                row["eval_" + key] = round(float(v), 5)
         hist.append(row)
         print(json.dumps(row), flush=True)
     wall = time.time() - t0
