@@ -333,7 +333,8 @@ int32_t lrl_sim_randomize_envs(lrl_sim* sim, int32_t first_env, int32_t num_envs
 int32_t lrl_sim_step(lrl_sim* sim, const float* actions, uint32_t flags, void* stream);
 
 /* Launch timing of the fused env kernel (bench.py roofline): enable = 1 starts recording HIP events around each
- * env-kernel launch of lrl_sim_step on its stream (the history-shift launch before it is outside); the next call
+ * env-kernel launch of lrl_sim_step on its stream (the history-shift launch before it is outside; the metrics launch
+ * after it, when lrl_sim_metrics_enable switched it on, is inside: one event pair per step either way); the next call
  * returns the summed milliseconds and the launch count of the recorded launches (waiting for them) and
  * restarts (enable = 1) or stops (enable = 0) recording. */
 int32_t lrl_sim_timing(lrl_sim* sim, int32_t enable, double* total_ms, int64_t* launches);
@@ -421,6 +422,58 @@ int32_t lrl_sim_refresh_rigid_body_state(lrl_sim* sim, void* stream);
 #define LRL_EXTRAS_TORQUES 65
 #define LRL_EXTRAS_ROWS 77
 int32_t lrl_sim_extras_snapshot(lrl_sim* sim, float* out, void* stream);
+
+/* ---- evaluation metrics on the device (the reference's mini_gym_learn/eval_metrics/metrics.py METRICS_FNS, one
+ * device -> host copy per metric and step there): with metrics enabled, lrl_sim_step launches one more small kernel
+ * after the env kernel on the step's stream.  It reads the step's post-physics state (before any reset_idx) and writes
+ * a per-step table, rows of n floats at the LRL_METRIC_* ids, float32 in the reference's operation order:
+ *   LIN_VEL_RMSD sqrt((base_lin_vel_x - commands_0)^2), ANG_VEL_RMSD sqrt((base_ang_vel_z - commands_2)^2),
+ *   LIN_VEL_X, ANG_VEL_YAW, BASE_HEIGHT mean over the scan points of root_z - measured_height (root_z without
+ *   measure_heights), MAX_TORQUES max_k |tau_k|, POWER_CONSUMPTION sum_k tau_k qd_k,
+ *   COT P / ((base_mass + payload) 9.8 |base_lin_vel_xy|) (IEEE inf / nan at zero speed), FROUDE_NUMBER
+ *   v_x^2 / (9.8 0.30), TERMINATION the reset flag, and the internal row SPEED_XY |base_lin_vel_xy|.
+ * It also updates per-env totals since the last clear, each env its own column (no atomics): the fp64 sum and sum of
+ * squares of every row except COT (whose columns stay 0: a standing robot's inf / nan never enters a total; the
+ * episode cost of transport is sum P / (m g sum SPEED_XY), from the sums), the fp32 running max of every row (fmax:
+ * a nan is skipped), and int32 counts of steps, episodes (reset flags) and falls (reset flags that are not time-outs).
+ * The tables are the sim's own allocation, made by the first lrl_sim_metrics_enable(sim, 1): a sim that never enables
+ * metrics keeps its arena and its launches. */
+enum lrl_metric {
+  LRL_METRIC_LIN_VEL_RMSD = 0, LRL_METRIC_ANG_VEL_RMSD, LRL_METRIC_LIN_VEL_X, LRL_METRIC_ANG_VEL_YAW,
+  LRL_METRIC_BASE_HEIGHT, LRL_METRIC_MAX_TORQUES, LRL_METRIC_POWER_CONSUMPTION, LRL_METRIC_COT,
+  LRL_METRIC_FROUDE_NUMBER, LRL_METRIC_TERMINATION, LRL_METRIC_NUM,
+  LRL_METRIC_SPEED_XY = LRL_METRIC_NUM, /* internal: the denominator of the episode cost of transport */
+  LRL_METRIC_ROWS
+};
+/* Device pointers of the tables for zero-copy wrapping: every table has `rows` (LRL_METRIC_ROWS) rows of `pitch`
+ * elements (the padded env count), of which the first num_envs are written; the counters are one row. */
+typedef struct lrl_metrics_view {
+  float* step;     /* f32 [rows][pitch]: the last step's values */
+  double* sum;     /* f64 [rows][pitch] */
+  double* sumsq;   /* f64 [rows][pitch] */
+  float* max;      /* f32 [rows][pitch], -inf after a clear */
+  int32_t* steps;  /* i32 [pitch] */
+  int32_t* episodes;
+  int32_t* falls;
+  int32_t rows, named_rows; /* LRL_METRIC_ROWS, LRL_METRIC_NUM */
+  int32_t num_envs;
+  int64_t pitch;
+} lrl_metrics_view;
+/* on != 0: allocate (first time; the totals start cleared) and launch the metrics kernel in every later
+ * lrl_sim_step; on == 0: stop launching it (tables and totals are kept).  With lrl_sim_timing, the metrics launch is
+ * inside the step's event pair. */
+int32_t lrl_sim_metrics_enable(lrl_sim* sim, int32_t on);
+/* Zero the totals of the envs [0, num_envs) on `stream` (sums 0, max -inf, counts 0); the step table is left. */
+int32_t lrl_sim_metrics_clear(lrl_sim* sim, void* stream);
+/* LRL_E_INVALID before the first lrl_sim_metrics_enable(sim, 1). */
+int32_t lrl_sim_metrics_tensors(lrl_sim* sim, lrl_metrics_view* out);
+/* Pool the totals over the envs [first, first + count) (the train group, the eval group or all) in one workgroup:
+ * fp64, a fixed thread-stride order and an LDS tree, so two calls give the same bits.  out_dev: device f64
+ * [LRL_METRICS_REDUCE_DOUBLES]: (sum, sum of squares, max) of row r at 3 r, then the step, episode and fall counts and
+ * sum_e (base_mass + payload_e) * sum SPEED_XY_e (kg m/s-steps: 9.8 times it divides the pooled sum P for the group's
+ * cost of transport).  An empty range gives zeros and max -inf. */
+#define LRL_METRICS_REDUCE_DOUBLES (3 * LRL_METRIC_ROWS + 4)
+int32_t lrl_sim_metrics_reduce(lrl_sim* sim, int32_t first, int32_t count, double* out_dev, void* stream);
 
 /* ---- the upstream step without a host round trip (lrl/env.py, legacy_fork=False, one process): id lists and their
  * counts stay on the device; `nmax` bounds a device count `dcount` (launch size).

@@ -58,6 +58,10 @@ hipError_t lrl_launch_randomize(const KState*, int32_t, int32_t, const float*, c
 hipError_t lrl_launch_render(const KParams*, const KState*, const KRender*, const lrl_camera*, int32_t, uint8_t*, float*,
                              int32_t*, const int32_t*, hipStream_t);
 hipError_t lrl_launch_record_state(const KState*, int32_t, int32_t, int32_t*, hipStream_t);
+hipError_t lrl_launch_metrics(const KParams*, const KState*, const KMetrics*, int, hipStream_t);
+hipError_t lrl_launch_metrics_clear(const KState*, const KMetrics*, hipStream_t);
+hipError_t lrl_launch_metrics_reduce(const KParams*, const KState*, const KMetrics*, int32_t, int32_t, double*,
+                                     hipStream_t);
 }
 
 struct lrl_sim {
@@ -84,6 +88,10 @@ struct lrl_sim {
   size_t ev_used = 0;
   uint32_t garbage_mode = 0, garbage_pat = 0;  // lrl_debug_sim_garbage
   KRender rt;  // lrl_sim_render's model tables
+  // evaluation metrics (lrl_sim_metrics_*): the tables' own allocation (null until first enabled) and the step's switch
+  void* metrics_mem = nullptr;
+  KMetrics M = {};
+  bool metrics_on = false;
 };
 
 // What the camera draws of the model (include/lrl.h): the pose body of every sphere with a radius, and the end points
@@ -559,6 +567,7 @@ int32_t lrl_sim_destroy(lrl_sim* s) {
   (void)hipFree(s->d_hull);
   (void)hipFree(s->self_stats);
   (void)hipFree(s->d_code);
+  (void)hipFree(s->metrics_mem);
   for (auto& pr : s->ev) {
     (void)hipEventDestroy(pr.first);
     (void)hipEventDestroy(pr.second);
@@ -613,6 +622,9 @@ int32_t lrl_sim_step(lrl_sim* s, const float* actions, uint32_t flags, void* str
   const uint32_t kflags = (flags & ~LRL_STEP_KGROUP) | (s->hk.eval_group ? LRL_STEP_KGROUP : 0u);
   HIPCHECK(lrl_launch_env_step(s->dk, &s->S, s->lds_bytes, actions, kflags, s->step_counter, s->hk.p.terrain_mesh, s->mesh_tgs,
                                (hipStream_t)stream));
+  if (s->metrics_on)
+    HIPCHECK(lrl_launch_metrics(s->dk, &s->S, &s->M, s->hk.p.measure_heights && s->hk.p.num_height_points > 0,
+                                (hipStream_t)stream));
   if (tp) HIPCHECK(hipEventRecord(tp->second, (hipStream_t)stream));
   return 0;
 }
@@ -814,6 +826,65 @@ int32_t lrl_sim_extras_snapshot(lrl_sim* s, float* out, void* stream) {
   if (!s || !out) return fail(LRL_E_INVALID, "lrl_sim_extras_snapshot: null argument");
   HIPCHECK(lrl_launch_extras_snapshot(s->dk, &s->S, s->d_body_leg, s->d_body_link, s->d_foot_xyz, out,
                                       (hipStream_t)stream));
+  return 0;
+}
+
+int32_t lrl_sim_metrics_enable(lrl_sim* s, int32_t on) {
+  if (!s) return fail(LRL_E_INVALID, "null sim");
+  if (on && !s->metrics_mem) {
+    HIPCHECK(hipSetDevice(s->device));
+    // one allocation, every table 256-B aligned (rows of S.stride elements, a multiple of 64): sum, sumsq (f64),
+    // step, max (f32), then the three counters
+    const size_t N = (size_t)s->S.stride, R = LRL_METRIC_ROWS;
+    const size_t bytes = 2 * R * N * sizeof(double) + 2 * R * N * sizeof(float) + 3 * N * sizeof(int32_t);
+    void* mem = nullptr;
+    if (hipMalloc(&mem, bytes) != hipSuccess) return fail(LRL_E_NOMEM, "hipMalloc %zu bytes (metrics tables)", bytes);
+    s->metrics_mem = mem;
+    s->M.sum = (double*)mem;
+    s->M.sumsq = s->M.sum + R * N;
+    s->M.step = (float*)(s->M.sumsq + R * N);
+    s->M.max = s->M.step + R * N;
+    s->M.steps = (int32_t*)(s->M.max + R * N);
+    s->M.episodes = s->M.steps + N;
+    s->M.falls = s->M.episodes + N;
+    HIPCHECK(hipMemset(mem, 0, bytes));
+    HIPCHECK(lrl_launch_metrics_clear(&s->S, &s->M, nullptr));
+    HIPCHECK(hipStreamSynchronize(nullptr));
+  }
+  s->metrics_on = on != 0;
+  return 0;
+}
+
+int32_t lrl_sim_metrics_clear(lrl_sim* s, void* stream) {
+  if (!s) return fail(LRL_E_INVALID, "null sim");
+  if (!s->metrics_mem) return fail(LRL_E_INVALID, "lrl_sim_metrics_clear: metrics were never enabled");
+  HIPCHECK(lrl_launch_metrics_clear(&s->S, &s->M, (hipStream_t)stream));
+  return 0;
+}
+
+int32_t lrl_sim_metrics_tensors(lrl_sim* s, lrl_metrics_view* out) {
+  if (!s || !out) return fail(LRL_E_INVALID, "lrl_sim_metrics_tensors: null argument");
+  if (!s->metrics_mem) return fail(LRL_E_INVALID, "lrl_sim_metrics_tensors: metrics were never enabled");
+  out->step = s->M.step;
+  out->sum = s->M.sum;
+  out->sumsq = s->M.sumsq;
+  out->max = s->M.max;
+  out->steps = s->M.steps;
+  out->episodes = s->M.episodes;
+  out->falls = s->M.falls;
+  out->rows = LRL_METRIC_ROWS;
+  out->named_rows = LRL_METRIC_NUM;
+  out->num_envs = s->S.n;
+  out->pitch = s->S.stride;
+  return 0;
+}
+
+int32_t lrl_sim_metrics_reduce(lrl_sim* s, int32_t first, int32_t count, double* out_dev, void* stream) {
+  if (!s || !out_dev) return fail(LRL_E_INVALID, "lrl_sim_metrics_reduce: null argument");
+  if (!s->metrics_mem) return fail(LRL_E_INVALID, "lrl_sim_metrics_reduce: metrics were never enabled");
+  if (first < 0 || count < 0 || first > s->S.n || count > s->S.n - first)
+    return fail(LRL_E_INVALID, "env range [%d, %d + %d) outside the sim's %d envs", first, first, count, s->S.n);
+  HIPCHECK(lrl_launch_metrics_reduce(s->dk, &s->S, &s->M, first, count, out_dev, (hipStream_t)stream));
   return 0;
 }
 

@@ -127,3 +127,12 @@ struct KState {
   const float* inj_push;   // [n][2] injected _push_robots uniforms
   const float* inj_reset;  // [n_ids][5] (motor strength, Kp, Kd, x, y) uniforms of an injected reset_idx
 };
+
+// Evaluation-metrics tables of a sim (lrl_metrics.hip, include/lrl.h lrl_metrics_view): allocated by the first
+// lrl_sim_metrics_enable, outside the arena; every row has S.stride elements.
+struct KMetrics {
+  float* step;
+  double *sum, *sumsq;
+  float* max;
+  int32_t *steps, *episodes, *falls;
+};

@@ -97,6 +97,21 @@ class LrlTensor(C.Structure):
                 ("strides", C.c_int64 * 4)]
 
 
+# enum lrl_metric (lrl_sim_metrics_*): the named rows in id order, then the internal row of the tables
+METRIC_NAMES = ("lin_vel_rmsd", "ang_vel_rmsd", "lin_vel_x", "ang_vel_yaw", "base_height", "max_torques",
+                "power_consumption", "CoT", "froude_number", "termination")
+METRIC_NUM = len(METRIC_NAMES)
+METRIC_SPEED_XY = METRIC_NUM
+METRIC_ROWS = METRIC_NUM + 1
+METRICS_REDUCE_DOUBLES = 3 * METRIC_ROWS + 4
+
+
+class LrlMetricsView(C.Structure):
+    """lrl_metrics_view (lrl_sim_metrics_tensors)."""
+    _fields_ = [(k, C.c_void_p) for k in ("step", "sum", "sumsq", "max", "steps", "episodes", "falls")] + \
+               [("rows", i32), ("named_rows", i32), ("num_envs", i32), ("pitch", C.c_int64)]
+
+
 class LrlRolloutStore(C.Structure):
     _fields_ = [("obs", C.c_void_p), ("priv", C.c_void_p), ("hist", C.c_void_p), ("actions", C.c_void_p),
                 ("values", C.c_void_p), ("logp", C.c_void_p), ("mu", C.c_void_p), ("sigma", C.c_void_p),
@@ -196,7 +211,7 @@ _lib = None
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 # the files and order of csrc/Makefile's SRC_HASH (SRCS then HDRS)
 _HASHED = ["lrl_env.hip", "lrl_aux.hip", "lrl_gae.hip", "lrl_gemm.hip", "lrl_ppo.hip", "lrl_capi.cpp", "lrl_curriculum.cpp",
-           "lrl_curriculum_dev.hip", "lrl_env_flat.hip", "lrl_render.hip", "lrl_env_mesh_tgs.hip", "lrl_kparams.h", "lrl_gemm.h", "../../include/lrl.h", "../../include/lrl_philox.h",
+           "lrl_curriculum_dev.hip", "lrl_env_flat.hip", "lrl_render.hip", "lrl_env_mesh_tgs.hip", "lrl_metrics.hip", "lrl_kparams.h", "lrl_gemm.h", "../../include/lrl.h", "../../include/lrl_philox.h",
            "Makefile"]  # (the build flags too: a library built with other flags is stale)
 
 
@@ -240,7 +255,8 @@ def lib():
                      "lrl_sim_terrain_curriculum_dev", "lrl_sim_reset_idx_dev", "lrl_sim_observe_idx_dev",
                      "lrl_rows_mean_zero_dev", "lrl_sim_curriculum_resample_dev", "lrl_debug_gemm_paths",
                      "lrl_debug_sim_garbage", "lrl_debug_sim_arena", "lrl_sim_render", "lrl_sim_record",
-                     "lrl_debug_sim_lds_bytes"]:
+                     "lrl_debug_sim_lds_bytes", "lrl_sim_metrics_enable", "lrl_sim_metrics_clear",
+                     "lrl_sim_metrics_tensors", "lrl_sim_metrics_reduce"]:
             getattr(L, name).restype = C.c_int32
         L.lrl_np_sum_f64.restype = C.c_double
         L.lrl_np_sum_f64.argtypes = [C.c_void_p, C.c_int64]

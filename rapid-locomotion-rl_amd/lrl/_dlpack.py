@@ -35,6 +35,8 @@ _PyCapsule_New.restype = C.py_object
 _PyCapsule_New.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
 
 _CODE = {0: (2, 32), 1: (0, 32), 2: (1, 8)}  # lrl dtype -> (DLPack code, bits): f32, i32, u8
+F64 = 3  # host-side only (no lrl_tensor of the ABI has it): the fp64 metric totals, wrapped by lrl/eval_metrics.py
+_CODE[F64] = (2, 64)
 
 _keepalive = []  # descriptors must outlive the tensors; sims are few and long-lived
 

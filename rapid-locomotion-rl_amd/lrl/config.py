@@ -172,15 +172,70 @@ def _register_paths(sec, path=""):
             _register_paths(v, f"{path}.{k}" if path else k)
 
 
-def eval_variant(cfg, num_envs, sets=()):
+def _dr_preset(friction, restitution, added_mass, com, motor_strength):
+    """One evaluation preset of the domain randomisation: the five ranges that differ between the presets; the switches,
+    the (unused) Kp / Kd ranges and the push settings are the same in all of them."""
+    return {
+        "domain_rand.randomize_friction": True, "domain_rand.friction_range": friction,
+        "domain_rand.randomize_restitution": True, "domain_rand.restitution_range": restitution,
+        "domain_rand.restitution": 0.5,
+        "domain_rand.randomize_base_mass": True, "domain_rand.added_mass_range": added_mass,
+        "domain_rand.randomize_com_displacement": True, "domain_rand.com_displacement_range": com,
+        "domain_rand.randomize_motor_strength": True, "domain_rand.motor_strength_range": motor_strength,
+        "domain_rand.randomize_Kp_factor": False, "domain_rand.Kp_factor_range": [0.8, 1.3],
+        "domain_rand.randomize_Kd_factor": False, "domain_rand.Kd_factor_range": [0.5, 1.5],
+        "domain_rand.push_robots": False, "domain_rand.push_interval_s": 15, "domain_rand.max_push_vel_xy": 1.0,
+    }
+
+
+# Evaluation presets: cfg path -> value, the settings of the reference's mini_gym_learn/eval_metrics/
+# domain_randomization.py (DR_SETTINGS and base_set; tests/golden/dr_settings.json holds what its functions assign).
+# The six DR presets touch only what an eval group may change (lrl/params.py GROUP_FIELDS and the rigid-body
+# draws at creation), so each one works as an eval_cfg beside a training cfg.  "base_set" does not: the episode length
+# and the terminal body height are per-step kernel parameters shared by both groups, so it is for a stand-alone
+# evaluation env (scripts/evaluate.py), and as an eval_cfg lrl.params.eval_group_params refuses it.
+EVAL_PRESETS = {
+    "base_set": {
+        "terrain.teleport_robots": True, "terrain.border_size": 50, "terrain.num_rows": 10, "terrain.num_cols": 10,
+        "commands.resampling_time": 1e9, "env.episode_length_s": 500,
+        "rewards.terminal_body_height": 0.0, "rewards.use_terminal_body_height": True,
+    },
+    "rand_regular": _dr_preset([0.05, 4.5], [0, 1.0], [-1.0, 3.0], [-0.1, 0.1], [0.9, 1.1]),
+    "rand_large": _dr_preset([0.04, 6.0], [0, 1.0], [-1.5, 4.0], [-0.13, 0.13], [0.88, 1.12]),
+    # motor_strength_range [0.9, -0.99] is the reference's value (by the other presets' pattern [0.9, 0.91] was
+    # meant): kept, so the motor strengths are drawn from (-0.99, 0.9], sign changes included
+    "static_low": _dr_preset([0.05, 0.06], [0, 0.01], [-1.0, -0.99], [-0.1, -0.09], [0.9, -0.99]),
+    "static_medium": _dr_preset([1.0, 1.01], [0.5, 0.51], [0.0, 0.01], [0.0, 0.01], [1.0, 1.01]),
+    "static_high": _dr_preset([4.49, 4.5], [0.99, 1.0], [2.99, 3.0], [0.09, 0.1], [1.09, 1.1]),
+    "only_base_mass": _dr_preset([1.0, 1.01], [0.5, 0.51], [-1, 3], [0.0, 0.01], [1.0, 1.01]),
+}
+DR_PRESETS = tuple(k for k in EVAL_PRESETS if k != "base_set")
+
+
+def preset_sets(name):
+    """A preset as ``--eval-set`` strings (``PATH=VALUE``, the value's python literal)."""
+    if name not in EVAL_PRESETS:
+        raise KeyError(f"unknown evaluation preset {name!r}; known: {', '.join(EVAL_PRESETS)}")
+    return [f"{path}={value!r}" for path, value in EVAL_PRESETS[name].items()]
+
+
+def eval_variant(cfg, num_envs, sets=(), preset=None):
     """An eval cfg for ``LeggedRobotEnv(cfg=cfg, eval_cfg=...)``: an independent copy of ``cfg`` with ``num_envs`` envs
     and the assignments ``sets`` applied, each a string ``PATH=VALUE`` (scripts/train.py --eval-set) whose value is a
     python literal: ``domain_rand.friction_range=[0.05,0.06]``, ``domain_rand.push_robots=True``.  PATH must name an
-    existing field (a typo would otherwise evaluate on the training distribution without a word)."""
+    existing field (a typo would otherwise evaluate on the training distribution without a word).
+
+    ``preset``: the name of an ``EVAL_PRESETS`` entry (or several, applied in order) set before ``sets``, so an explicit
+    set overrides it.  The DR presets give a valid eval_cfg; ``base_set`` changes per-step kernel parameters (episode
+    length, terminal body height) and therefore only suits a stand-alone evaluation env, whose cfg the result then is."""
     import ast
     ecfg = copy.deepcopy(cfg)
     _register_paths(ecfg)
     ecfg.env.num_envs = int(num_envs)
+    for name in ((preset,) if isinstance(preset, str) else tuple(preset or ())):
+        if name not in EVAL_PRESETS:
+            raise KeyError(f"unknown evaluation preset {name!r}; known: {', '.join(EVAL_PRESETS)}")
+        _apply(ecfg, EVAL_PRESETS[name])  # (may add domain_rand.restitution, as the robot presets do)
     for item in sets:
         path, sep, text = str(item).partition("=")
         if not sep:

@@ -36,6 +36,9 @@ class RunnerArgs(ArgsProto):
     load_run = -1
     checkpoint = -1
     resume_path = None
+    # with eval envs: accumulate the device-side evaluation metrics (lrl.eval_metrics) over each evaluation batch and
+    # log their summary under eval/metrics/* before the eval envs are reset (project-only; off: nothing changes)
+    log_eval_metrics = False
 
 
 class Logger(ML_Logger):
@@ -72,6 +75,10 @@ class Runner:
         self.last_recording_it = 0
         self.logger = logger if logger is not None else _ml_logger  # (the reference: `from ml_logger import logger`)
         self.env.reset()
+        self.eval_metrics = None  # (enabled after the reset's zero-action step: a batch counts the rollout steps only)
+        if getattr(self.args, "log_eval_metrics", False) and getattr(self.env, "num_eval_envs", 0) > 0:
+            from ..eval_metrics import EvalMetrics
+            self.eval_metrics = EvalMetrics(self.env).enable()
 
     def learn(self, num_learning_iterations, init_at_random_ep_len=False, eval_freq=100, eval_expert=False):
         lg = self.logger
@@ -99,6 +106,10 @@ class Runner:
                                 lg.store_metrics(**infos[key])
                 self.alg.compute_returns(obs[:n_train], priv[:n_train])
                 if it % eval_freq == 0:
+                    if self.eval_metrics is not None:  # the batch since the last evaluation reset, then a fresh one
+                        with lg.Prefix(metrics="eval/metrics"):
+                            lg.store_metrics(self.eval_metrics.summary("eval"))
+                        self.eval_metrics.clear()
                     self.env.reset_evaluation_envs()
             mv, ms, ma = self.alg.update()
             lg.store_metrics(time_elapsed=lg.since("start"), time_iter=lg.split("epoch"), adaptation_loss=ma,

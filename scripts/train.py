@@ -10,8 +10,10 @@ eval/episode, whose cfg is a copy of the train cfg with every PATH=VALUE applied
 cfg may differ in command ranges and in domain randomisation, pushes and teleport; e.g. a narrow
 low-friction evaluation without pushes:
   --eval-envs 512 --eval-set domain_rand.friction_range=[0.05,0.06] --eval-set domain_rand.push_robots=False
+--eval-preset NAME is sugar over --eval-set: one of the reference's evaluation DR presets (lrl.config.DR_PRESETS:
+rand_regular, rand_large, static_low, static_medium, static_high, only_base_mass), applied before the explicit sets.
 usage: python scripts/train.py [--iterations N] [--robot mc|go1] [--root DIR] [--terrain-tgs]
-                               [--eval-envs N [--eval-set PATH=VALUE ...]]"""
+                               [--eval-envs N [--eval-preset NAME] [--eval-set PATH=VALUE ...]]"""
 import argparse
 import os
 import sys
@@ -63,9 +65,15 @@ if __name__ == "__main__":
     ap.add_argument("--eval-set", action="append", default=[], metavar="PATH=VALUE",
                     help="set a field of the eval cfg (a copy of the train cfg), e.g. "
                          "domain_rand.friction_range=[0.05,0.06]; repeatable")
+    from lrl.config import DR_PRESETS, preset_sets
+    ap.add_argument("--eval-preset", default=None, choices=list(DR_PRESETS), metavar="NAME",
+                    help="an evaluation DR preset for the eval cfg (%s), set before the --eval-set items"
+                         % ", ".join(DR_PRESETS))
     a = ap.parse_args()
-    if a.eval_set and not a.eval_envs:
-        ap.error("--eval-set needs --eval-envs")
+    if (a.eval_set or a.eval_preset) and not a.eval_envs:
+        ap.error("--eval-set / --eval-preset need --eval-envs")
+    if a.eval_preset:
+        a.eval_set = preset_sets(a.eval_preset) + a.eval_set
     from ml_logger import logger
     from mini_gym import MINI_GYM_ROOT_DIR
 
