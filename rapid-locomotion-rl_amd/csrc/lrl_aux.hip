@@ -8,6 +8,7 @@
 
 #include "../../include/lrl_philox.h"
 #include "lrl_kparams.h"
+#include "lrl_launch.h"
 
 namespace lrl {
 

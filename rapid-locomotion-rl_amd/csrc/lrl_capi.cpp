@@ -9,7 +9,9 @@
 
 #include <vector>
 
+#include "lrl_env_layout.h"
 #include "lrl_kparams.h"
+#include "lrl_launch.h"
 
 static thread_local char g_err[512];
 static int fail(int code, const char* fmt, ...) {
@@ -26,43 +28,6 @@ extern "C" int lrl_set_error(int code, const char* msg) { return fail(code, "%s"
     hipError_t e_ = (x);                                                                \
     if (e_ != hipSuccess) return fail(LRL_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); \
   } while (0)
-
-extern "C" {
-hipError_t lrl_launch_env_step(const KParams*, const KState*, int, const float*, uint32_t, int64_t, int, int,
-                               hipStream_t);
-hipError_t lrl_launch_observe(const KParams*, const KState*, const int32_t*, int32_t, const int32_t*, uint32_t, int64_t,
-                              hipStream_t);
-hipError_t lrl_env_kernel_setup(int lds_bytes);
-hipError_t lrl_launch_reset(const KParams*, const KState*, const int32_t*, int32_t, const int32_t*, int32_t, float, float,
-                            float, float, int32_t, hipStream_t);
-hipError_t lrl_launch_env_lists(const KState*, int32_t, int32_t, int32_t*, int32_t*, hipStream_t);
-hipError_t lrl_launch_curriculum_dev(const lrl_dev_curriculum*, const KState*, int32_t, const int32_t*, int32_t,
-                                     const int32_t*, int32_t, int32_t, int32_t, double, double, double, int32_t,
-                                     int32_t, hipStream_t);
-hipError_t lrl_launch_set_root(const KState*, const float*, const int32_t*, int32_t, hipStream_t);
-hipError_t lrl_launch_step_code(const KState*, int32_t, int32_t, int32_t, float*, int32_t*, hipStream_t);
-hipError_t lrl_launch_apply_commands(const KState*, int32_t, const int32_t*, int32_t, const float*, const float*, float*,
-                                     int32_t, hipStream_t);
-hipError_t lrl_launch_terrain_curriculum(const KState*, const int32_t*, int32_t, const int32_t*, int64_t*, const int64_t*,
-                                         const int64_t*, const float*, int32_t, int32_t, float, float, int32_t, int64_t,
-                                         hipStream_t);
-hipError_t lrl_launch_set_dof(const KState*, const float*, const float*, const int32_t*, int32_t, hipStream_t);
-hipError_t lrl_launch_rigid_body(const KParams*, const KState*, const int32_t*, const int32_t*, const float*,
-                                 hipStream_t);
-hipError_t lrl_launch_extras_snapshot(const KParams*, const KState*, const int32_t*, const int32_t*, const float*, float*,
-                                      hipStream_t);
-hipError_t lrl_launch_shift_history(const KState*, int, int, int, hipStream_t);
-hipError_t lrl_launch_garbage(uint32_t mode, uint32_t pat, hipStream_t st);
-hipError_t lrl_launch_randomize(const KState*, int32_t, int32_t, const float*, const float*, const float*, const float*,
-                                uint32_t, hipStream_t);
-hipError_t lrl_launch_render(const KParams*, const KState*, const KRender*, const lrl_camera*, int32_t, uint8_t*, float*,
-                             int32_t*, const int32_t*, hipStream_t);
-hipError_t lrl_launch_record_state(const KState*, int32_t, int32_t, int32_t*, hipStream_t);
-hipError_t lrl_launch_metrics(const KParams*, const KState*, const KMetrics*, int, hipStream_t);
-hipError_t lrl_launch_metrics_clear(const KState*, const KMetrics*, hipStream_t);
-hipError_t lrl_launch_metrics_reduce(const KParams*, const KState*, const KMetrics*, int32_t, int32_t, double*,
-                                     hipStream_t);
-}
 
 struct lrl_sim {
   int device = 0;
@@ -403,23 +368,12 @@ int32_t lrl_sim_create(const lrl_model* model, const lrl_env_params* params, int
   HIPCHECK(hipMemcpy(s->d_body_leg, model->body_leg, sizeof(int32_t) * LRL_MAX_BODIES, hipMemcpyHostToDevice));
   HIPCHECK(hipMemcpy(s->d_body_link, model->body_link, sizeof(int32_t) * LRL_MAX_BODIES, hipMemcpyHostToDevice));
   HIPCHECK(hipMemcpy(s->d_foot_xyz, model->foot_xyz, sizeof(float) * 12, hipMemcpyHostToDevice));
-  // env step kernel LDS: wg_envs envs per workgroup: leg blocks + contact rows, or the obs tiles
-  const int wg_envs = params->terrain_mesh ? LRL_ENV_WG_ENVS_MESH : LRL_ENV_WG_ENVS_FLAT;
+  // env step kernel LDS: the byte count of the map the sim's build of the kernel addresses (lrl_env_layout.h)
   s->mesh_tgs = params->terrain_mesh && params->solver_tgs && params->solver_iterations > 0;
-  const int legf = s->mesh_tgs ? LRL_LEGF_MESH_TGS : params->terrain_mesh ? LRL_LEGF_MESH : LRL_LEGF_FLAT;
-  const int nsf = params->terrain_mesh ? LRL_NSF_MESH : LRL_NSF_FLAT;
-  int lds_contacts = (4 * legf + model->num_spheres * nsf) * wg_envs * 4;  // LEGF, NSF of lrl_env.hip
-  // terrain query vertex block, float4 [16][lanes]; the joint-limit rows (12 x 19 fields per env) alias it after the
-  // queries, and have their own region on the plane
-  // (the mesh TGS build: that block and the work list as one scratch that also takes the restitution targets)
-  lds_contacts += s->mesh_tgs           ? LRL_MESH_TGS_SCRATCH(model->num_spheres) * 4
-                  : params->terrain_mesh ? 16 * LRL_ENV_LANES * 16
-                                         : LRL_NUM_DOF * LRL_LIMF * wg_envs * 4;
-  lds_contacts += (4 * (int)(sizeof(KLeg) / 4) + 5 * model->num_spheres) * 4;  // staged model tables (Lds::ktab)
-  lds_contacts += (40 + s->hk.self_npairs + 1) * 4;  // + the self-collision groups and pairs
-  if (params->terrain_mesh && !s->mesh_tgs) lds_contacts += LRL_ENV_LANES * 20;  // + the terrain query work list (Lds::wl)
-  int lds_tiles = (NO + LRL_NUM_PRIV + LRL_MAX_REWARD_TERMS) * wg_envs * 4;  // obs / priv tiles + reward rows
-  s->lds_bytes = lds_contacts > lds_tiles ? lds_contacts : lds_tiles;
+  const lrl_env_build& build = s->mesh_tgs           ? lrl_env_builds::mesh_tgs
+                               : params->terrain_mesh ? lrl_env_builds::mesh
+                                                      : lrl_env_builds::plane;
+  s->lds_bytes = lrl_env_lds_layout(build, model->num_spheres, s->hk.self_npairs, NO).bytes;
   if (s->lds_bytes > 160 * 1024) return fail(LRL_E_INVALID, "LDS budget exceeded (%d B)", s->lds_bytes);
   HIPCHECK(lrl_env_kernel_setup(s->lds_bytes));
   // tensor descriptors: [n, k] views over SoA [k][N] -> strides (1, N)

@@ -19,8 +19,7 @@
 #include <vector>
 
 #include "../../include/lrl.h"
-
-extern "C" int lrl_set_error(int code, const char* msg);  // lrl_capi.cpp
+#include "lrl_launch.h"
 
 namespace {
 

@@ -18,6 +18,7 @@
 
 #include "../../include/lrl.h"
 #include "lrl_kparams.h"
+#include "lrl_launch.h"
 
 namespace lrl {
 

@@ -1,7 +1,10 @@
-// lrl_env.hip — fused LeggedRobot.step for gfx950 (CDNA4).
+// lrl_env_step.h — fused LeggedRobot.step for gfx950 (CDNA4): the device code of the env step kernel.  Not a translation
+// unit: each build's file (lrl_env_flat.hip, lrl_env_mesh.hip, lrl_env_mesh_tgs.hip) defines LRL_ENV_BUILD as the name
+// of its lrl_env_build (lrl_env_layout.h), includes this header and expands LRL_ENV_ENTRY_POINTS at its end.  Without
+// LRL_ENV_BUILD only the build-independent helpers are defined (lrl_env_dispatch.hip's observe_kernel shares them).
 //
 // A quad of lanes per env (layout below: 16 envs per single-wave workgroup on the terrain mesh, 4 envs with four
-// mirrored quads each on the plane, lrl_env_flat.hip).  A launch performs the whole policy step
+// mirrored quads each on the plane).  A launch performs the whole policy step
 // (legged_robot.py:106-137): action clip, `decimation` x {PD torques (:653-688) + one physics
 // sub-step}, post_physics_step (:139-188) with teleport (:768-791), DR redraw (:544-560, :591-593),
 // termination (:190-202), rewards (:314-340, :1506-1646), observations + noise (:342-417), the
@@ -24,77 +27,10 @@
 #include <stdint.h>
 
 #include "../../include/lrl_philox.h"
-#include "lrl_kparams.h"
-
-#define BLOCK LRL_ENV_LANES  // lanes per workgroup (one wave; see lrl_kparams.h)
-// Quad layout: 4 lanes per env (lane & 3 = the leg it owns), 16 envs per single-wave workgroup (the mesh build).  The leg
-// work (kinematics, composite inertias, leg blocks, RNEA, contact detection and Delassus rows of the leg's
-// spheres, warm-start impulses) runs leg-parallel; the base quantities are summed over the 4 lanes with
-// cross-lane shuffles; the Gauss-Seidel sweep and the integration run redundantly in the 4 lanes (so
-// every lane holds the full env state); post-physics runs in lane 0 of each env.
-#define QL 4
-// Plane build (lrl_env_flat.hip includes this file with LRL_ENV_FLAT_TU): 4 envs per wave, 16 lanes per env = 4
-// mirrored quads.  Every quad of an env runs the quad code above on the same data (identical values, identical
-// stores), and the per-sphere work — ground detection and Delassus row setup — is split over the 4 quads (a lane
-// takes every 4th of the spheres its leg owns), so those loops run a quarter of the spheres per lane; the wave's
-// loops over max-over-envs contact counts run over 4 envs instead of 16; 1,024 single-wave workgroups fill every
-// SIMD of the chip (the 16-env form leaves 3 of each CU's 4 SIMDs idle).  The terrain-mesh build keeps 16 envs per
-// wave: its rows do not fit 4 workgroups' LDS per CU.
-// Terrain-mesh TGS build (lrl_env_mesh_tgs.hip includes this file with LRL_ENV_MESH_TGS_TU): the mesh layout, with the
-// TGS solver of the plane build compiled in unconditionally (lrl_launch_env_step launches it only for solver_tgs with
-// solver_iterations > 0) and room for its fields (lrl_kparams.h); the PGS mesh build stays as it is.
-// ENV_TGS: the build's solver — 0 PGS only, 1 PGS or TGS by KParams::p.solver_tgs, 2 TGS only.
-#if defined(LRL_ENV_FLAT_TU)
-#define ENVS LRL_ENV_WG_ENVS_FLAT
-#define LRL_ENV_NS flat
-#define ENV_TGS 1
-#elif defined(LRL_ENV_MESH_TGS_TU)
-#define ENVS (BLOCK / QL)
-#define LRL_ENV_NS mesh_tgs
-#define ENV_TGS 2
-#else
-#define ENVS (BLOCK / QL)
-#define LRL_ENV_NS mesh
-#define ENV_TGS 0
-#endif
-#define MIRROR (BLOCK / (QL * ENVS))  // quads per env
-static_assert(MIRROR == 1 || MIRROR == 4, "an env has one quad or four mirrored quads");
-#define NSF (MIRROR > 1 ? LRL_NSF_FLAT : LRL_NSF_MESH)  // LDS fields per contact sphere (map above contact_setup)
-#define LIMF LRL_LIMF  // LDS fields per joint-limit row (map above limit_setup)
+#include "lrl_env_layout.h"
+#include "lrl_launch.h"
 
 namespace lrl {
-inline namespace LRL_ENV_NS {
-
-// XCD-aware env blocks: the hardware deals workgroup ids round-robin over the 8 XCDs, so block b is renumbered to
-// the env block it covers with consecutive env blocks on one XCD.  A wave's SoA field access is 16 envs x 4 B = half
-// a 128-B line; with the plain mapping the two halves of each line were read (and written) through two different
-// XCD L2s, each fetching the whole line.
-__device__ __forceinline__ int env_block() {
-  const int nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-}
-
-// Phase timers (build with -DLRL_ENV_PROFILE; read with lrl_debug_env_profile): per-wave shader-clock
-// cycles of the step kernel's phases, summed over waves.
-#ifdef LRL_ENV_PROFILE
-__device__ unsigned long long g_env_prof[24];
-#define LRL_PROF_DECL unsigned long long prof_t = clock64();
-#define LRL_PROF(i)                                   \
-  {                                                   \
-    const unsigned long long t_ = clock64();          \
-    prof[i] += t_ - prof_t;                           \
-    prof_t = t_;                                      \
-  }
-#else
-#define LRL_PROF_DECL
-#define LRL_PROF(i)
-#endif
-// Terrain-contact debug records (build with -DLRL_ENV_DEBUG; buffer set with lrl_debug_env_buffer): per env and
-// sphere 8 floats — candidate flag, separation found, world centre (x, y, z), window max, radius, 1 — of the last
-// sub-step of the launch (scripts/terrain_debug.py runs one sub-step per launch).
-#ifdef LRL_ENV_DEBUG
-__device__ float* g_env_dbg;
-#endif
 
 struct V3 {
   float x, y, z;
@@ -202,6 +138,75 @@ __device__ __forceinline__ float sv_get(const SV& s, int r) {
   return r == 0 ? s.a.x : r == 1 ? s.a.y : r == 2 ? s.a.z : r == 3 ? s.l.x : r == 4 ? s.l.y : s.l.z;
 }
 
+#ifdef LRL_ENV_BUILD
+#define BLOCK LRL_ENV_LANES  // lanes per workgroup (one wave; see lrl_kparams.h)
+// Quad layout: 4 lanes per env (lane & 3 = the leg it owns), 16 envs per single-wave workgroup (the mesh build).  The leg
+// work (kinematics, composite inertias, leg blocks, RNEA, contact detection and Delassus rows of the leg's
+// spheres, warm-start impulses) runs leg-parallel; the base quantities are summed over the 4 lanes with
+// cross-lane shuffles; the Gauss-Seidel sweep and the integration run redundantly in the 4 lanes (so
+// every lane holds the full env state); post-physics runs in lane 0 of each env.
+#define QL 4
+// Plane build (lrl_env_builds::plane): 4 envs per wave, 16 lanes per env = 4
+// mirrored quads.  Every quad of an env runs the quad code above on the same data (identical values, identical
+// stores), and the per-sphere work — ground detection and Delassus row setup — is split over the 4 quads (a lane
+// takes every 4th of the spheres its leg owns), so those loops run a quarter of the spheres per lane; the wave's
+// loops over max-over-envs contact counts run over 4 envs instead of 16; 1,024 single-wave workgroups fill every
+// SIMD of the chip (the 16-env form leaves 3 of each CU's 4 SIMDs idle).  The terrain-mesh build keeps 16 envs per
+// wave: its rows do not fit 4 workgroups' LDS per CU.
+// Terrain-mesh TGS build (lrl_env_builds::mesh_tgs): the mesh layout, with the TGS solver of the plane build compiled in
+// unconditionally (lrl_launch_env_step launches it only for solver_tgs with solver_iterations > 0) and room for its
+// fields (lrl_env_layout.h); the PGS mesh build stays as it is.
+#define LRL_CAT_(a, b) a##b
+#define LRL_CAT(a, b) LRL_CAT_(a, b)
+#define LRL_STR_(a) #a
+#define LRL_STR(a) LRL_STR_(a)
+#define LRL_ENV_NS LRL_CAT(LRL_ENV_NS_, LRL_ENV_BUILD)
+#define LIMF LRL_LIMF  // LDS fields per joint-limit row (map above limit_setup)
+
+inline namespace LRL_ENV_NS {
+
+// everything build-specific below derives from this one description (lrl_env_layout.h)
+constexpr lrl_env_build kBuild = lrl_env_builds::LRL_ENV_BUILD;
+static_assert(lrl_env_build_known(kBuild) && lrl_str_eq(kBuild.ns, LRL_STR(LRL_ENV_NS)),
+              "the env kernel has three builds: plane, mesh, mesh_tgs");
+constexpr int ENVS = kBuild.envs;         // envs per workgroup
+constexpr int MIRROR = kBuild.mirror();   // quads per env
+constexpr int ENV_TGS = kBuild.solver;    // 0 PGS only, 1 PGS or TGS by KParams::p.solver_tgs, 2 TGS only
+constexpr int NSF = kBuild.nsf();         // LDS fields per contact sphere (map above contact_setup)
+constexpr int LEGF = kBuild.legf();       // LDS fields per leg block (map above Lds)
+static_assert(MIRROR == 1 || MIRROR == 4, "an env has one quad or four mirrored quads");
+
+// XCD-aware env blocks: the hardware deals workgroup ids round-robin over the 8 XCDs, so block b is renumbered to
+// the env block it covers with consecutive env blocks on one XCD.  A wave's SoA field access is 16 envs x 4 B = half
+// a 128-B line; with the plain mapping the two halves of each line were read (and written) through two different
+// XCD L2s, each fetching the whole line.
+__device__ __forceinline__ int env_block() {
+  const int nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+}
+
+// Phase timers (build with -DLRL_ENV_PROFILE; read with lrl_debug_env_profile): per-wave shader-clock
+// cycles of the step kernel's phases, summed over waves.
+#ifdef LRL_ENV_PROFILE
+__device__ unsigned long long g_env_prof[24];
+#define LRL_PROF_DECL unsigned long long prof_t = clock64();
+#define LRL_PROF(i)                                   \
+  {                                                   \
+    const unsigned long long t_ = clock64();          \
+    prof[i] += t_ - prof_t;                           \
+    prof_t = t_;                                      \
+  }
+#else
+#define LRL_PROF_DECL
+#define LRL_PROF(i)
+#endif
+// Terrain-contact debug records (build with -DLRL_ENV_DEBUG; buffer set with lrl_debug_env_buffer): per env and
+// sphere 8 floats — candidate flag, separation found, world centre (x, y, z), window max, radius, 1 — of the last
+// sub-step of the launch (scripts/terrain_debug.py runs one sub-step per launch).
+#ifdef LRL_ENV_DEBUG
+__device__ float* g_env_dbg;
+#endif
+
 // Per-leg solver blocks live in LDS as [leg][field][lane] columns (each lane owns one column, so
 // the accesses are bank-conflict free).  Field map inside a leg (LEGF floats):
 //   0..8  joint axes a_j (base frame)   9..17 joint origins o_j   18..35 K = D^-1 B^T (3x6)
@@ -209,38 +214,40 @@ __device__ __forceinline__ float sv_get(const SV& s, int r) {
 //   45..47 leg joint rates at the start of the contact solve   48..50 Y = sum of D^-1 p_l over the
 //   impulses applied to this leg (lazy propagation: qd_l = qd0_l + Y_l - K_l (v_b - v_b0))
 //   51..53 (TGS builds) dz = sum over the sub-iterations of h (q0_l + Y_l) = the leg's joint motion + K_l dx_b
-#define LEGF (MIRROR > 1 ? LRL_LEGF_FLAT : ENV_TGS == 2 ? LRL_LEGF_MESH_TGS : LRL_LEGF_MESH)
 #define LF_DZ 51
 #define LI(r, c) ((r) * ((r) + 1) / 2 + (c))
 
-#define KLEGF ((int)(sizeof(KLeg) / sizeof(float)))  // floats of one leg's model table
+#define KLEGF LRL_KLEGF  // floats of one leg's model table
+// A lane's view of the workgroup's LDS: the regions of lrl_env_lds_layout (lrl_env_layout.h), which the launch's byte
+// count comes from too
 struct Lds {
   float* base;     // leg blocks, then contact rows: [field][env slot] columns shared by the env's 4 lanes
-  int sph_off;     // field offset of the contact rows
+  lrl_env_lds L;   // region offsets in floats
   int es;          // env slot of this lane inside the workgroup
-  float* ktab;     // the model tables a lane reads at a lane-dependent index, staged once per launch:
-                   // K->leg[4], then per sphere (x, y, z, radius), then per sphere its link (int)
   int nsph;
-  int lim_off;     // field offset of the joint-limit rows (LIM_* map below contact_pgs_q)
-  float* wl;       // terrain query work list (after the staged tables): [BLOCK] candidate masks, [BLOCK] offsets,
-                   // [BLOCK] masks of the candidates found in contact
-  __device__ __forceinline__ float* wlist() const { return wl; }
-  __device__ __forceinline__ const KLeg& kleg(int l) const { return reinterpret_cast<const KLeg*>(ktab)[l]; }
+  // the model tables a lane reads at a lane-dependent index, staged once per launch: K->leg[4], then per sphere
+  // (x, y, z, radius), then per sphere its link (int)
+  __device__ __forceinline__ float* ktab() const { return base + L.ktab; }
+  // terrain query work list: [BLOCK] candidate masks, [BLOCK] offsets, [BLOCK] masks of the candidates found in contact
+  __device__ __forceinline__ float* wlist() const { return base + L.wl; }
+  // the terrain query's vertex blocks
+  __device__ __forceinline__ float4* tverts() const { return reinterpret_cast<float4*>(base + L.scratch); }
+  __device__ __forceinline__ const KLeg& kleg(int l) const { return reinterpret_cast<const KLeg*>(ktab())[l]; }
   __device__ __forceinline__ float4 sph4(int s) const {
-    return reinterpret_cast<const float4*>(ktab + 4 * KLEGF)[s];
+    return reinterpret_cast<const float4*>(ktab() + 4 * KLEGF)[s];
   }
   // per sphere: its link (low byte, sign-extended: -1 on the base) | (its support table + 1) << 8 (lrl_model::sphere_hull)
   __device__ __forceinline__ int slink_raw(int s) const {
-    return reinterpret_cast<const int*>(ktab + 4 * KLEGF + 4 * nsph)[s];
+    return reinterpret_cast<const int*>(ktab() + 4 * KLEGF + 4 * nsph)[s];
   }
   __device__ __forceinline__ int slink(int s) const { return (slink_raw(s) << 24) >> 24; }
   // the terrain query's radius of sphere s: its own, or 0 for a support-table collider (its query point is the
   // support point)
   __device__ __forceinline__ float qrad(int s) const { return (slink_raw(s) >> 8) ? 0.f : sph4(s).w; }
   // self-collision groups [lane][g][begin, end) (KParams::self_grp) and pairs (KParams::self_pair), after the links
-  __device__ __forceinline__ const int* sgrp() const { return reinterpret_cast<const int*>(ktab + 4 * KLEGF + 5 * nsph); }
+  __device__ __forceinline__ const int* sgrp() const { return reinterpret_cast<const int*>(base + L.sgrp); }
   __device__ __forceinline__ uint32_t spair(int p) const {
-    return reinterpret_cast<const uint32_t*>(ktab + 4 * KLEGF + 5 * nsph + 40)[p];
+    return reinterpret_cast<const uint32_t*>(base + L.spair)[p];
   }
   // field f of a row = row pointer + f * ENVS (a constant f folds into the ds_read / ds_write immediate offset)
   __device__ __forceinline__ float& leg(int l, int f) const { return lp(l)[f * ENVS]; }
@@ -251,16 +258,17 @@ struct Lds {
   }
   // column pointers: field f of the row is p[f * ENVS] (constant offsets fold into the ds_read / ds_write
   // immediate instead of one address computation per field)
-  __device__ __forceinline__ float* sp(int s) const { return base + (sph_off + s * NSF) * ENVS + es; }
+  __device__ __forceinline__ float* sp(int s) const { return base + L.sph + s * NSF * ENVS + es; }
+  // (the leg blocks start the LDS: lrl_env_lds::leg is 0)
   __device__ __forceinline__ float* lp(int l) const { return base + l * LEGF * ENVS + es; }
-  __device__ __forceinline__ float* lm(int r) const { return base + (lim_off + r * LIMF) * ENVS + es; }
+  __device__ __forceinline__ float* lm(int r) const { return base + L.lim + r * LIMF * ENVS + es; }
   // (TGS) the restitution target of sphere s: the row's last field on the plane; on the mesh [sphere][env slot] after
-  // the joint-limit rows, in the query scratch (LRL_MESH_TGS_SCRATCH, lrl_kparams.h)
+  // the joint-limit rows, in the query scratch (lrl_env_lds::br)
   __device__ __forceinline__ float* br(int s) const {
     if constexpr (MIRROR > 1)
       return sp(s) + (NSF - 1) * ENVS;
     else
-      return base + (lim_off + LRL_NUM_DOF * LIMF + s) * ENVS + es;
+      return base + L.br + s * ENVS + es;
   }
   __device__ __forceinline__ float Kx(int l, int j, int r) const { return leg(l, 18 + 6 * j + r); }
   __device__ __forceinline__ float Di(int l, int k) const { return leg(l, 36 + k); }
@@ -1774,7 +1782,7 @@ __device__ void substep(const KParams* __restrict__ K, Body& st, const float* ta
 #ifdef LRL_ENV_PROFILE
       prof[22] += clock64() - tq0;  // scan + work-list publication
 #endif
-      float4* tv = reinterpret_cast<float4*>(M.base + (M.sph_off + K->num_spheres * NSF) * ENVS);
+      float4* tv = M.tverts();
       // item j -> (owner lane L, sphere s): the last lane whose prefix is <= j, then the owner's (j - prefix)-th set bit.
       // Located one round ahead: round r + 1's chain of dependent LDS reads runs under round r's query
       auto locate = [&](int j, int& L, int& s) {
@@ -1792,7 +1800,7 @@ __device__ void substep(const KParams* __restrict__ K, Body& st, const float* ta
         if (j < total) {
           const int L = Ln, s = sn;
           if (j + BLOCK < total) locate(j + BLOCK, Ln, sn);
-          float* row = M.base + (M.sph_off + s * NSF) * ENVS + (L >> 2);
+          float* row = M.base + M.L.sph + s * NSF * ENVS + (L >> 2);
           const THit th = terrain_query(K, v3(row[6 * ENVS], row[7 * ENVS], row[8 * ENVS]), M.qrad(s),
                                         P.contact_offset, tv, lane, prof);
 #ifdef LRL_ENV_PROFILE
@@ -2141,8 +2149,11 @@ __device__ void substep(const KParams* __restrict__ K, Body& st, const float* ta
   LRL_PROF(4)  // integration
 }
 
+}  // namespace LRL_ENV_NS
+#endif  // LRL_ENV_BUILD
+
 // ------------------------------------------------------------------------------------------------
-// post-physics helpers: torch op order, no contraction
+// post-physics helpers: torch op order, no contraction (build-independent; observe_kernel in lrl_env_dispatch.hip uses them too)
 // ------------------------------------------------------------------------------------------------
 #pragma clang fp contract(off)
 __device__ __forceinline__ float act_scaled(const lrl_env_params& P, const float* act, int j) {
@@ -2278,6 +2289,10 @@ __device__ __forceinline__ void priv_row(const lrl_env_params& P, const KState& 
   for (int i = 0; i < LRL_NUM_PRIV; ++i) pr[i] = fminf(fmaxf(pr[i], -P.clip_obs), P.clip_obs);
 }
 
+#ifdef LRL_ENV_BUILD
+inline namespace LRL_ENV_NS {
+
+// (TERR restates kBuild.terrain: the parameter is kept for the kernel's symbol name, which the profiling scripts match)
 template <bool TERR>
 __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restrict__ K, KState S,
                                                         const float* __restrict__ actions_in, uint32_t flags,
@@ -2339,20 +2354,16 @@ __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restri
     ms3[j] = S.motor_strength[jj * N + e];
     lqd3[j] = ctl == 1 ? S.last_dof_vel[jj * N + e] : 0.f;
   }
-  // leg blocks first, then the contact rows, (terrain: the query's vertex block), then the model tables
-  const int nsph = K->num_spheres;
+  // the LDS map: leg blocks, contact rows, (terrain: the query's scratch), the model tables (lrl_env_layout.h)
+  static_assert(TERR == kBuild.terrain, "the template parameter restates the build");
   static_assert(LRL_NUM_DOF * LIMF * ENVS <= 64 * BLOCK, "joint-limit rows must fit the terrain vertex blocks");
-  // (mesh TGS build: the query's work list ends the scratch, ahead of the tables, so that the restitution targets can
-  // run from the vertex blocks' tail into its dead part: LRL_MESH_TGS_SCRATCH)
-  const int scratch = ENV_TGS == 2 ? LRL_MESH_TGS_SCRATCH(nsph) : TERR ? 64 * BLOCK : LRL_NUM_DOF * LIMF * ENVS;
-  float* const ktab = lds + (4 * LEGF + nsph * NSF) * ENVS + scratch;
-  const Lds M{lds, 4 * LEGF, es, ktab, nsph, 4 * LEGF + nsph * NSF,
-              ENV_TGS == 2 ? ktab - 5 * BLOCK : ktab + ((4 * KLEGF + 5 * nsph + 40 + K->self_npairs + 1) & ~1)};
+  const int nsph = K->num_spheres;
+  const Lds M{lds, lrl_env_lds_layout(kBuild, nsph, K->self_npairs, P.num_obs), es, nsph};
   {
     const float* src = reinterpret_cast<const float*>(K->leg);
-    for (int i = lane; i < 4 * KLEGF; i += BLOCK) M.ktab[i] = src[i];
-    float4* s4 = reinterpret_cast<float4*>(M.ktab + 4 * KLEGF);
-    int* sl = reinterpret_cast<int*>(M.ktab + 4 * KLEGF + 4 * nsph);
+    for (int i = lane; i < 4 * KLEGF; i += BLOCK) M.ktab()[i] = src[i];
+    float4* s4 = reinterpret_cast<float4*>(M.ktab() + 4 * KLEGF);
+    int* sl = reinterpret_cast<int*>(M.ktab() + 4 * KLEGF + 4 * nsph);
     for (int s = lane; s < nsph; s += BLOCK) {
       s4[s] = make_float4(K->sph_pos[s][0], K->sph_pos[s][1], K->sph_pos[s][2], K->sph_rad[s]);
       sl[s] = (K->sph_link[s] & 0xff) | ((K->sph_hull[s] + 1) << 8);  // (base: link byte 0xff = -1, no table)
@@ -2523,8 +2534,10 @@ __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restri
   __syncthreads();  // LDS contact rows are dead from here on; the obs tile reuses them
   LRL_PROF(10)  // contact forces per body
   const int NO = P.num_obs;
-  float* otile = lds;                    // [ENVS][NO]
-  float* ptile = lds + ENVS * NO;        // [ENVS][18]
+  // (the map again, for its tiles: M.L's would keep num_obs live through the physics)
+  const lrl_env_lds TL = lrl_env_lds_layout(kBuild, nsph, K->self_npairs, NO);
+  float* otile = lds + TL.otile;  // [ENVS][NO]
+  float* ptile = lds + TL.ptile;  // [ENVS][18]
   // The env's group (lrl_sim_set_eval_group; _call_train_eval, legged_robot.py:456-469).  Without an eval block the
   // three per-group blocks below take p's values and nothing else is read: grp_on is a bit of the launch's flags
   // (LRL_STEP_KGROUP, set by lrl_sim_step), so the default path pays one wave-uniform branch per block and no load.
@@ -2722,7 +2735,7 @@ __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restri
   // rewards
   // per-term rewards go to an LDS row first (the contact rows are dead): no global traffic inside the term
   // loop, so the episode / command sum updates below can keep all their loads in flight at once
-  float* rt = lds + ENVS * (NO + LRL_NUM_PRIV) + es * LRL_MAX_REWARD_TERMS;
+  float* rt = lds + TL.rtile + es * LRL_MAX_REWARD_TERMS;
   float rew = 0.f;
   for (int t = 0; t < P.num_reward_terms; ++t) {
     float r = 0.f;
@@ -2909,17 +2922,14 @@ __global__ __launch_bounds__(BLOCK) void env_step_kernel(const KParams* __restri
 #endif
 }
 
-}  // namespace LRL_ENV_NS
-}  // namespace lrl
-
-#ifdef LRL_ENV_FLAT_TU
-// the plane build's entry points (lrl_env_flat.hip); lrl_launch_env_step & co. below dispatch to them
-extern "C" int lrl_debug_env_profile_flat(unsigned long long* out, int reset) {
+// ---- host side of the build (the extern "C" names: LRL_ENV_ENTRY_POINTS below) ----
+// the phase timers of this build, optionally zeroed after the read: 24 values (0: not a profile build)
+static int env_profile(unsigned long long* out, int reset) {
 #ifdef LRL_ENV_PROFILE
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(lrl::g_env_prof), sizeof(unsigned long long) * 24) != hipSuccess) return -2;
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_env_prof), sizeof(unsigned long long) * 24) != hipSuccess) return -2;
   if (reset) {
     unsigned long long z[24] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(lrl::g_env_prof), z, sizeof(z)) != hipSuccess) return -2;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_env_prof), z, sizeof(z)) != hipSuccess) return -2;
   }
   return 24;
 #else
@@ -2928,247 +2938,36 @@ extern "C" int lrl_debug_env_profile_flat(unsigned long long* out, int reset) {
   return 0;
 #endif
 }
-
-extern "C" hipError_t lrl_env_kernel_setup_flat(int lds_bytes) {
-  return hipFuncSetAttribute((const void*)lrl::env_step_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             lds_bytes);
-}
-
-extern "C" hipError_t lrl_launch_env_step_flat(const KParams* K, const KState* S, int lds_bytes, const float* actions,
-                                               uint32_t flags, int64_t step_counter, hipStream_t stream) {
-  hipLaunchKernelGGL(lrl::env_step_kernel<false>, dim3(S->stride / ENVS), dim3(BLOCK), lds_bytes, stream, K, *S,
-                     actions, flags, step_counter);
-  return hipGetLastError();
-}
-#elif defined(LRL_ENV_MESH_TGS_TU)
-// the terrain-mesh TGS build's entry points (lrl_env_mesh_tgs.hip); lrl_launch_env_step & co. dispatch to them
-extern "C" int lrl_debug_env_profile_mesh_tgs(unsigned long long* out, int reset) {
-#ifdef LRL_ENV_PROFILE
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(lrl::g_env_prof), sizeof(unsigned long long) * 24) != hipSuccess) return -2;
-  if (reset) {
-    unsigned long long z[24] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(lrl::g_env_prof), z, sizeof(z)) != hipSuccess) return -2;
-  }
-  return 24;
-#else
-  (void)out;
-  (void)reset;
-  return 0;
-#endif
-}
-
-extern "C" int lrl_debug_env_buffer_mesh_tgs(float* buf) {
+// (the plane kernel writes no debug records: its buffer stays unset)
+static int env_debug_buffer(float* buf) {
 #ifdef LRL_ENV_DEBUG
-  return hipMemcpyToSymbol(HIP_SYMBOL(lrl::g_env_dbg), &buf, sizeof(buf)) == hipSuccess ? 1 : -2;
+  if (!kBuild.terrain) return 1;
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_env_dbg), &buf, sizeof(buf)) == hipSuccess ? 1 : -2;
 #else
   (void)buf;
   return 0;
 #endif
 }
 
-extern "C" hipError_t lrl_env_kernel_setup_mesh_tgs(int lds_bytes) {
-  return hipFuncSetAttribute((const void*)lrl::env_step_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             lds_bytes);
-}
-
-extern "C" hipError_t lrl_launch_env_step_mesh_tgs(const KParams* K, const KState* S, int lds_bytes,
-                                                   const float* actions, uint32_t flags, int64_t step_counter,
-                                                   hipStream_t stream) {
-  hipLaunchKernelGGL(lrl::env_step_kernel<true>, dim3(S->stride / ENVS), dim3(BLOCK), lds_bytes, stream, K, *S,
-                     actions, flags, step_counter);
-  return hipGetLastError();
-}
-#else
-extern "C" int lrl_debug_env_profile_flat(unsigned long long* out, int reset);
-extern "C" hipError_t lrl_env_kernel_setup_flat(int lds_bytes);
-extern "C" hipError_t lrl_launch_env_step_flat(const KParams* K, const KState* S, int lds_bytes, const float* actions,
-                                               uint32_t flags, int64_t step_counter, hipStream_t stream);
-extern "C" int lrl_debug_env_profile_mesh_tgs(unsigned long long* out, int reset);
-extern "C" int lrl_debug_env_buffer_mesh_tgs(float* buf);
-extern "C" hipError_t lrl_env_kernel_setup_mesh_tgs(int lds_bytes);
-extern "C" hipError_t lrl_launch_env_step_mesh_tgs(const KParams* K, const KState* S, int lds_bytes,
-                                                   const float* actions, uint32_t flags, int64_t step_counter,
-                                                   hipStream_t stream);
-
-// the sum of the three builds' timers (a simulation runs one of them)
-extern "C" int lrl_debug_env_profile(unsigned long long* out, int reset) {
-#ifdef LRL_ENV_PROFILE
-  unsigned long long f[24], g[24];
-  if (lrl_debug_env_profile_flat(f, reset) != 24) return -2;
-  if (lrl_debug_env_profile_mesh_tgs(g, reset) != 24) return -2;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(lrl::g_env_prof), sizeof(unsigned long long) * 24) != hipSuccess) return -2;
-  for (int i = 0; i < 24; ++i) out[i] += f[i] + g[i];
-  if (reset) {
-    unsigned long long z[24] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(lrl::g_env_prof), z, sizeof(z)) != hipSuccess) return -2;
-  }
-  return 24;
-#else
-  (void)out;
-  (void)reset;
-  return 0;
-#endif
-}
-
-extern "C" int lrl_debug_env_buffer(float* buf) {
-#ifdef LRL_ENV_DEBUG
-  if (lrl_debug_env_buffer_mesh_tgs(buf) != 1) return -2;
-  return hipMemcpyToSymbol(HIP_SYMBOL(lrl::g_env_dbg), &buf, sizeof(buf)) == hipSuccess ? 1 : -2;
-#else
-  (void)buf;
-  return 0;
-#endif
-}
-
-extern "C" hipError_t lrl_env_kernel_setup(int lds_bytes) {
-  hipError_t e = lrl_env_kernel_setup_flat(lds_bytes);
-  if (e != hipSuccess) return e;
-  e = lrl_env_kernel_setup_mesh_tgs(lds_bytes);
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute((const void*)lrl::env_step_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             lds_bytes);
-}
-
-namespace lrl {
-inline namespace LRL_ENV_NS {
-// compute_observations for envs just reset inside a step (upstream semantics, legged_robot.py:177-184):
-// obs / priv rows from the post-reset state with the step's noise draws, the newest history slot, and the
-// last_* buffers post_physics_step sets after the reset (last_actions = actions, last_dof_vel = dof_vel,
-// last_root_vel = root velocity).  One thread per listed env.
-// 16 lanes per env (OBS_LANES): lane c forms, noises, clips and stores only its 4-wide chunks of the observation row
-// (chunk i0 / 4 on lane (i0 / 4) % 16: one Philox draw each instead of the whole row's draws on one thread), reading
-// the state entries those need; lane 0 writes the base-frame velocities, the privileged row and the last_* buffers.
-// Every element's value, draw and operation order are the step kernel's (obs_base_values + its quads' joint entries /
-// obs_noise_clip), so the rows are bit-identical.
-constexpr int OBS_LANES = 16;
-// observation entry i of env e (the step kernel's layout: [only lin vel,] [only ang vel,] [lin vel, ang vel,] gravity,
-// [commands,] dof pos, dof vel, actions, [yaw,] then the height rows against base height z)
-__device__ __forceinline__ float obs_entry(const lrl_env_params& P, const KState& S, int e, int i, V3 blv, V3 bav,
-                                           V3 pg) {
-  const int N = S.stride;
-  int o = 0;
-  if (P.observe_only_lin_vel) {
-    if (i < 3) return (i == 0 ? blv.x : i == 1 ? blv.y : blv.z) * P.obs_scale_lin_vel;
-    o = 3;
-  }
-  if (P.observe_only_ang_vel) {
-    if (i < o + 3) return (i == o ? bav.x : i == o + 1 ? bav.y : bav.z) * P.obs_scale_ang_vel;
-    o += 3;
-  }
-  if (P.observe_vel) {
-    if (i < o + 3)
-      return (P.global_reference ? S.root[(7 + i - o) * N + e] : (i == o ? blv.x : i == o + 1 ? blv.y : blv.z)) *
-             P.obs_scale_lin_vel;
-    if (i < o + 6) return (i == o + 3 ? bav.x : i == o + 4 ? bav.y : bav.z) * P.obs_scale_ang_vel;
-    o += 6;
-  }
-  if (i < o + 3) return i == o ? pg.x : i == o + 1 ? pg.y : pg.z;
-  o += 3;
-  if (P.observe_command) {
-    if (i < o + 3) return S.commands[(i - o) * N + e] * P.commands_scale[i - o];
-    o += 3;
-  }
-  if (i < o + 12) return (S.dof_pos[(i - o) * N + e] - P.default_dof_pos[i - o]) * P.obs_scale_dof_pos;
-  if (i < o + 24) return S.dof_vel[(i - o - 12) * N + e] * P.obs_scale_dof_vel;
-  if (i < o + 36) return S.actions[(i - o - 24) * N + e];
-  if (P.observe_yaw && i == o + 36) {
-    float q[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) q[k] = S.root[(3 + k) * N + e];
-    return obs_yaw_value(q);
-  }
-  const int k = i - (P.num_obs - P.num_height_points);  // height row k (measure_heights)
-  return fminf(fmaxf(S.root[2 * N + e] - 0.5f - S.heights[k * N + e], -1.f), 1.f) * P.obs_scale_height;
-}
-__global__ __launch_bounds__(256) void observe_kernel(const KParams* __restrict__ K, KState S,
-                                                      const int32_t* __restrict__ ids, int32_t n,
-                                                      const int32_t* __restrict__ dn, uint32_t flags,
-                                                      int64_t step_counter) {
-  const int gt = blockIdx.x * blockDim.x + threadIdx.x;
-  const int t = gt / OBS_LANES, c = gt % OBS_LANES;
-  if (t >= (dn ? min(*dn, n) : n)) return;  // (dn: device count, n its bound)
-  const int e = ids[t];
-  if (e < 0 || e >= S.n) return;
-  const lrl_env_params& P = K->p;
-  const int N = S.stride, NO = P.num_obs;
-  const uint64_t genv = (uint64_t)(S.env_offset + e);
-  const bool inject = (flags & LRL_STEP_INJECT_UNIFORM) != 0;
-  float quat[4], V[3], W[3];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) quat[k] = S.root[(3 + k) * N + e];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    V[k] = S.root[(7 + k) * N + e];
-    W[k] = S.root[(10 + k) * N + e];
-  }
-  const V3 blv = quat_rotate_inverse(quat, v3(V[0], V[1], V[2]));
-  const V3 bav = quat_rotate_inverse(quat, v3(W[0], W[1], W[2]));
-  const V3 pg = quat_rotate_inverse(quat, v3(0.f, 0.f, -1.f));
-  float* row = S.obs + (size_t)e * NO;
-  float* h = (flags & LRL_STEP_HISTORY) ? S.hist + (size_t)e * (K->num_history * NO) + (K->num_history - 1) * NO
-                                        : nullptr;
-  for (int i0 = 4 * c; i0 < NO; i0 += 4 * OBS_LANES) {
-    float v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = i0 + k < NO ? obs_entry(P, S, e, i0 + k, blv, bav, pg) : 0.f;
-    if (P.add_noise) {  // (obs_noise_clip's chunk i0 / 4)
-      lrl_u32x4 r = lrl_philox((uint32_t)genv, (uint32_t)step_counter,
-                               (LRL_RNG_OBS_NOISE << 16) ^ (uint32_t)(step_counter >> 32), (uint32_t)(i0 >> 2), S.seed);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int i = i0 + k;
-        if (i < NO) {
-          float u = inject ? (e < S.n ? S.inj_noise[(size_t)e * NO + i] : 0.5f) : lrl_u01(r.v[k]);
-          v[k] += (2.f * u - 1.f) * P.noise_vec[i];
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (i0 + k < NO) {
-        const float x = fminf(fmaxf(v[k], -P.clip_obs), P.clip_obs);
-        row[i0 + k] = x;
-        if (h) h[i0 + k] = x;
-      }
-  }
-  if (c != 0) return;
-  float ms[12];
-#pragma unroll
-  for (int j = 0; j < 12; ++j) ms[j] = S.motor_strength[j * N + e];
-  S.base_lin_vel[e] = blv.x; S.base_lin_vel[N + e] = blv.y; S.base_lin_vel[2 * N + e] = blv.z;
-  S.base_ang_vel[e] = bav.x; S.base_ang_vel[N + e] = bav.y; S.base_ang_vel[2 * N + e] = bav.z;
-  S.projected_gravity[e] = pg.x; S.projected_gravity[N + e] = pg.y; S.projected_gravity[2 * N + e] = pg.z;
-  priv_row(P, S, e, S.payload[e], v3(S.com[e], S.com[N + e], S.com[2 * N + e]), ms, S.priv + (size_t)e * LRL_NUM_PRIV);
-#pragma unroll
-  for (int j = 0; j < 12; ++j) {
-    S.last_actions[j * N + e] = S.actions[j * N + e];
-    S.last_dof_vel[j * N + e] = S.dof_vel[j * N + e];
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    S.last_root_vel[k * N + e] = V[k];
-    S.last_root_vel[(3 + k) * N + e] = W[k];
-  }
-}
 }  // namespace LRL_ENV_NS
+#endif  // LRL_ENV_BUILD
 }  // namespace lrl
 
-// mesh_tgs: the sim's parameters ask for TGS on the mesh (terrain_mesh, solver_tgs, solver_iterations > 0)
-extern "C" hipError_t lrl_launch_env_step(const KParams* K, const KState* S, int lds_bytes, const float* actions,
-                                          uint32_t flags, int64_t step_counter, int terrain_mesh, int mesh_tgs,
-                                          hipStream_t stream) {
-  if (!terrain_mesh) return lrl_launch_env_step_flat(K, S, lds_bytes, actions, flags, step_counter, stream);
-  if (mesh_tgs) return lrl_launch_env_step_mesh_tgs(K, S, lds_bytes, actions, flags, step_counter, stream);
-  hipLaunchKernelGGL(lrl::env_step_kernel<true>, dim3(S->stride / ENVS), dim3(BLOCK), lds_bytes, stream, K, *S,
-                     actions, flags, step_counter);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t lrl_launch_observe(const KParams* K, const KState* S, const int32_t* ids, int32_t n,
-                                         const int32_t* dn, uint32_t flags, int64_t step_counter, hipStream_t stream) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(lrl::observe_kernel, dim3((int)(((int64_t)n * lrl::OBS_LANES + 255) / 256)), dim3(256), 0, stream,
-                     K, *S, ids, n, dn, flags, step_counter);
-  return hipGetLastError();
-}
-#endif  // LRL_ENV_FLAT_TU / LRL_ENV_MESH_TGS_TU
+// The entry points of build b, declared in lrl_launch.h (LRL_ENV_ENTRY_DECLS); lrl_env_dispatch.hip dispatches to them.  A
+// build's file ends with LRL_ENV_ENTRY_POINTS(LRL_ENV_BUILD).
+#ifdef LRL_ENV_BUILD
+#define LRL_ENV_ENTRY_POINTS(b) LRL_ENV_ENTRY_POINTS_(b)
+#define LRL_ENV_ENTRY_POINTS_(b)                                                                                    \
+  extern "C" hipError_t lrl_launch_env_step_##b(const KParams* K, const KState* S, int lds_bytes, const float* actions, \
+                                                uint32_t flags, int64_t step_counter, hipStream_t stream) {         \
+    hipLaunchKernelGGL(lrl::env_step_kernel<lrl::kBuild.terrain>, dim3(S->stride / lrl::ENVS), dim3(BLOCK), lds_bytes, \
+                       stream, K, *S, actions, flags, step_counter);                                                \
+    return hipGetLastError();                                                                                       \
+  }                                                                                                                 \
+  extern "C" hipError_t lrl_env_kernel_setup_##b(int lds_bytes) {                                                   \
+    return hipFuncSetAttribute((const void*)lrl::env_step_kernel<lrl::kBuild.terrain>,                              \
+                               hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);                              \
+  }                                                                                                                 \
+  extern "C" int lrl_debug_env_profile_##b(unsigned long long* out, int reset) { return lrl::env_profile(out, reset); } \
+  extern "C" int lrl_debug_env_buffer_##b(float* buf) { return lrl::env_debug_buffer(buf); }
+#endif

@@ -10,8 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/lrl.h"
-
-extern "C" int lrl_set_error(int code, const char* msg);
+#include "lrl_launch.h"
 
 namespace lrl {
 

@@ -14,30 +14,6 @@
 #ifndef LRL_ENV_LANES
 #define LRL_ENV_LANES 64
 #endif
-// envs per workgroup: the terrain-mesh kernel keeps one quad per env (16 envs per wave); the plane kernel runs 4 envs
-// per wave, 16 lanes (4 mirrored quads) per env (lrl_env.hip, lrl_env_flat.hip)
-#define LRL_ENV_WG_ENVS_MESH (LRL_ENV_LANES / 4)
-#define LRL_ENV_WG_ENVS_FLAT (LRL_ENV_LANES / 16)
-// LDS fields per leg block / per contact-sphere row of the env kernel (lrl_env.hip): the plane build carries the TGS
-// solver's extra fields (the leg's accumulated joint-space motion dz, a contact's restitution target).  The terrain-mesh
-// PGS build has neither (its 16-env workgroup fills the CU's LDS).  The terrain-mesh TGS build (lrl_env_mesh_tgs.hip,
-// Cfg.sim.physx.terrain_solver_type 1) has dz in its leg blocks and keeps the restitution targets out of the rows, in
-// LDS that is dead during the solve: after the joint-limit rows in the terrain query's scratch (below)
-#define LRL_LEGF_MESH 51
-#define LRL_LEGF_MESH_TGS 54
-#define LRL_LEGF_FLAT 54
-#define LRL_NSF_MESH 67
-#define LRL_NSF_FLAT 68
-#define LRL_LIMF 19  // LDS fields per joint-limit row
-// The mesh TGS build's query scratch, in floats, for a model of nsph spheres: the vertex blocks (float4 [16][lanes])
-// followed by the query work list (5 floats per lane, its last 2 per lane the hit masks the activation reads).  Once a
-// sub-step's queries are done the joint-limit rows alias the start of it, as in the PGS build, and the restitution
-// targets ([sphere][env slot]) follow them; they may run over the dead part of the work list but not over the hit
-// masks, so a model with more spheres than that leaves room for gets a longer scratch.
-#define LRL_MESH_TGS_SCRATCH(nsph)                                                                       \
-  ((64 + 5) * LRL_ENV_LANES > (LRL_NUM_DOF * LRL_LIMF + (nsph)) * LRL_ENV_WG_ENVS_MESH + 2 * LRL_ENV_LANES \
-       ? (64 + 5) * LRL_ENV_LANES                                                                         \
-       : (LRL_NUM_DOF * LRL_LIMF + (nsph)) * LRL_ENV_WG_ENVS_MESH + 2 * LRL_ENV_LANES)
 
 struct KLeg {
   float xyz[3][3];   // joint origin in the parent frame
@@ -59,7 +35,7 @@ struct KParams {
   int32_t sph_link[LRL_MAX_SPHERES];  // 0..2 dynamic link inside the leg, -1 base
   int32_t sph_leg[LRL_MAX_SPHERES];   // 0..3, -1 base
   // mesh colliders (lrl_model::sphere_hull, ABI 6): support table of sphere s (-1: the sphere itself), the tables in
-  // device memory [hull][6][hull_res][hull_res][hull_k] float4 (lrl_env.hip hull_support; both builds)
+  // device memory [hull][6][hull_res][hull_res][hull_k] float4 (lrl_env_step.h hull_support; every build)
   int32_t sph_hull[LRL_MAX_SPHERES];
   const float* hull_tab;
   int32_t hull_res, hull_k;

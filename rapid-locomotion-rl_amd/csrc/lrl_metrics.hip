@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "lrl_kparams.h"
+#include "lrl_launch.h"
 
 namespace lrl {
 

@@ -28,8 +28,7 @@
 #include "../../include/lrl.h"
 #include "../../include/lrl_philox.h"
 #include "lrl_gemm.h"
-
-extern "C" int lrl_set_error(int code, const char* msg);
+#include "lrl_launch.h"
 
 namespace lrl {
 

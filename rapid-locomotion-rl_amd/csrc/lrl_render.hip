@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "lrl_kparams.h"
+#include "lrl_launch.h"
 
 namespace lrl {
 

@@ -1,7 +1,8 @@
 """Bit-identity check of a library change: runs the bench's workload (4096 Mini Cheetah envs, flat, fork semantics,
-random-init policy; or 4096 Go1 envs on the curriculum trimesh with `rough`) for a few PPO iterations under the
+random-init policy; or 4096 Go1 envs on the curriculum trimesh with `rough`, `rough_tgs`: the same with
+sim.physx.terrain_solver_type = 1, the mesh TGS build of the env kernel) for a few PPO iterations under the
 library LRL_LIB names and saves the env state and the policy parameters; `compare` diffs two such files.
-usage: LRL_LIB=... python scripts/ab_state.py run <out.npz> [iters] [mc|rough]
+usage: LRL_LIB=... python scripts/ab_state.py run <out.npz> [iters] [mc|rough|rough_tgs]
        python scripts/ab_state.py compare <a.npz> <b.npz>"""
 import os
 import sys
@@ -21,13 +22,15 @@ def run(out, iters=2, workload="mc"):
     n = 4096
     cfg = lcfg.make_cfg()
     legacy = True
-    if workload == "rough":
+    if workload in ("rough", "rough_tgs"):
         lcfg.config_go1(cfg)
         cfg.terrain.mesh_type = "trimesh"
         cfg.terrain.measure_heights = True
         cfg.terrain.curriculum = True
         cfg.env.num_observations = 42 + 187
         legacy = False
+        if workload == "rough_tgs":
+            cfg.sim.physx.terrain_solver_type = 1
     else:
         lcfg.config_mini_cheetah(cfg)
     cfg.env.num_envs = n

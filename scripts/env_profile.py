@@ -1,4 +1,4 @@
-"""Phase breakdown of the env step kernel (build: -DLRL_ENV_PROFILE, see csrc/lrl_env.hip; run with
+"""Phase breakdown of the env step kernel (build: -DLRL_ENV_PROFILE, see csrc/lrl_env_step.h; run with
 LRL_LIB=<that build>, e.g. `make -C rapid-locomotion-rl_amd/csrc liblrl_prof.so`).  4096 envs, random actions;
 argv: [n] [mc | go1 | go1_rough | go1_rough_tgs]
 (go1_rough_tgs: Cfg.sim.physx.terrain_solver_type = 1, the terrain-mesh TGS build)."""

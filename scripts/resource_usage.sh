@@ -5,8 +5,9 @@
 set -euo pipefail
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd "$ROOT/rapid-locomotion-rl_amd/csrc"
-for f in lrl_env.hip lrl_env_flat.hip lrl_env_mesh_tgs.hip lrl_aux.hip lrl_gae.hip lrl_gemm.hip lrl_ppo.hip lrl_curriculum_dev.hip; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast-honor-pragmas --cuda-device-only \
+for f in lrl_env_dispatch.hip lrl_env_flat.hip lrl_env_mesh.hip lrl_env_mesh_tgs.hip lrl_aux.hip lrl_gae.hip lrl_gemm.hip lrl_ppo.hip lrl_curriculum_dev.hip; do
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast-honor-pragmas \
+    -Xclang -target-feature -Xclang -packed-fp32-ops --cuda-device-only \
     -Rpass-analysis=kernel-resource-usage -c "$f" -o /tmp/lrl_res_$$.o 2>&1 |
     sed -n 's/.*remark: *//p' | sed 's/ \[-Rpass-analysis=kernel-resource-usage\]//' |
     awk -v F="$f" '/^Function Name:/ {printf "\n%s %s", F, $3; next}

@@ -1,4 +1,4 @@
-"""The non-step env kernels (csrc/lrl_aux.hip and observe_kernel of csrc/lrl_env.hip) against the independent
+"""The non-step env kernels (csrc/lrl_aux.hip and observe_kernel of csrc/lrl_env_dispatch.hip) against the independent
 references of tests/aux_ref.py, through the C ABI on sims made with lrl_sim_create.
 
 Forward kinematics (rigid_body_kernel, the foot rows of extras_snapshot_kernel) is held to ``aux_ref.fk`` in float64.
