@@ -1,5 +1,6 @@
 """Plain numpy references for the non-step env kernels (csrc/lrl_aux.hip, observe_kernel): the counter RNG, forward
-kinematics of the robot table, and the small list / shift / mean operations.  Nothing here imports the product; the
+kinematics of the robot table, and the small list / shift / mean operations; and for the draws the step and act
+kernels take from the counter RNG themselves (observation noise, pushes, the per-step redraw, policy noise).  Nothing here imports the product; the
 references work in float64 unless a ``dtype`` says otherwise, and tests/test_aux_ref.py pins them on facts from
 outside this repository's kernels (Random123's known answers, finite differences, closed forms).
 """
@@ -58,6 +59,112 @@ def terrain_level_draw(genv, step_counter, seed, max_level):
     step_counter = int(step_counter)
     r = philox(genv, step_counter & M32, ((RNG_TERRAIN << 16) ^ (step_counter >> 32)) & M32, 0, seed)
     return (r[0] * int(max_level)) >> 32
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The draws of the env step kernel and of the act kernels (csrc/lrl_env_step.h, observe_kernel, csrc/lrl_ppo.hip)
+# ---------------------------------------------------------------------------------------------------------------
+def step_key(stream, counter):
+    """Counter words 1 and 2 of a per-step draw: the counter's low word, and (stream << 16) ^ its high word."""
+    counter = int(counter)
+    return counter & M32, ((stream << 16) ^ (counter >> 32)) & M32
+
+
+def obs_noise_uniforms(genv, step_counter, seed, num_obs):
+    """The observation row's noise uniforms of global env ``genv`` at ``step_counter`` (the value after lrl_sim_step's
+    increment): entry i is word i & 3 of block i >> 2 on stream RNG_OBS_NOISE.  float32 [num_obs]."""
+    c1, c2 = step_key(RNG_OBS_NOISE, step_counter)
+    blocks = [philox(genv, c1, c2, b, seed) for b in range((num_obs + 3) >> 2)]
+    return np.array([u01(blocks[i >> 2][i & 3]) for i in range(num_obs)], np.float32)
+
+
+def push_uniforms(genv, step_counter, seed):
+    """_push_robots' x and y uniforms: words 0 and 1 of block 0 on stream RNG_PUSH.  float32 [2]."""
+    c1, c2 = step_key(RNG_PUSH, step_counter)
+    r = philox(genv, c1, c2, 0, seed)
+    return np.array([u01(r[0]), u01(r[1])], np.float32)
+
+
+def dr_uniforms(genv, step_counter, seed, on_ms, on_kp, on_kd):
+    """The per-step redraw's uniforms (motor strength, Kp, Kd) and the word each one took: words of block 0 on stream
+    RNG_DR handed out in that order to the switches that are on; a switch that is off consumes no word (NaN, -1)."""
+    c1, c2 = step_key(RNG_DR, step_counter)
+    r = philox(genv, c1, c2, 0, seed)
+    u, word = np.full(3, np.nan, np.float32), np.full(3, -1, np.int64)
+    k = 0
+    for i, on in enumerate((on_ms, on_kp, on_kd)):
+        if on:
+            u[i], word[i] = u01(r[k]), k
+            k += 1
+    return u, word
+
+
+TWO_PI_F32 = np.float32(6.283185307179586)
+U1_FLOOR = np.float32(1e-7)
+
+
+def box_muller(u1, u2, odd):
+    """Box-Muller in float64 from float32 uniforms (arrays or scalars): u1 clamped from below at float32(1e-7), the
+    angle float32(2 pi) * u2 rounded once to float32 as the kernels round it; rad = sqrt(-2 ln u1), the even member of
+    a pair takes rad cos, the odd one rad sin.  Returns (normal, rad)."""
+    u1 = np.maximum(np.asarray(u1, np.float32), U1_FLOOR)
+    th = (TWO_PI_F32 * np.asarray(u2, np.float32)).astype(np.float32).astype(np.float64)
+    rad = np.sqrt(-2.0 * np.log(u1.astype(np.float64)))
+    return np.where(odd, rad * np.sin(th), rad * np.cos(th)), rad
+
+
+def policy_normals(grow, counter, seed, na):
+    """The act kernels' policy noise of global row ``grow`` at act counter ``counter``: action j draws from words 0
+    and 1 of block j >> 1 on stream RNG_POLICY (a pair of actions shares a block).  float64 (normals [na], rad [na])."""
+    c1, c2 = step_key(RNG_POLICY, counter)
+    blocks = [philox(grow, c1, c2, b, seed) for b in range((na + 1) >> 1)]
+    j = np.arange(na)
+    u1 = np.array([u01(blocks[i >> 1][0]) for i in j], np.float32)
+    u2 = np.array([u01(blocks[i >> 1][1]) for i in j], np.float32)
+    return box_muller(u1, u2, (j & 1) == 1)
+
+
+def policy_noise_bound(rad, e_ref, mu_over_sd=0.0):
+    """The bar on |(a - mu) / sd - e_ref|: 8 x 2^-24 rad (logf, sqrtf and sinf / cosf at 2 ulp each plus the product's
+    rounding, all relative to the radius) + 4 x 2^-24 (|mu| / sd + |e_ref|) (the roundings of mu + sd e and of the
+    subtraction that recovers the noise)."""
+    return 2.0 ** -24 * (8.0 * np.asarray(rad) + 4.0 * (np.abs(mu_over_sd) + np.abs(e_ref)))
+
+
+def log_prob_terms(a, mu, sd):
+    """Per action, in float64 from the given values: the Gaussian log-density and the magnitude sum d^2 / (2 sd^2) +
+    |ln sd| + ln sqrt(2 pi) that its float32 evaluation's error scales with."""
+    a, mu, sd = (np.asarray(x, np.float64) for x in (a, mu, sd))
+    q = (a - mu) ** 2 / (2.0 * sd * sd)
+    half_log_2pi = 0.5 * np.log(2.0 * np.pi)
+    return -q - np.log(sd) - half_log_2pi, q + np.abs(np.log(sd)) + half_log_2pi
+
+
+# the same generator on numpy uint64 arrays: for searches over keys and for row counts where the integer form is slow
+def philox_v(c0, c1, c2, c3, seed):
+    """``philox`` on broadcastable integer arrays: uint32 words [..., 4]."""
+    m = np.uint64(M32)
+    c0, c1, c2, c3 = np.broadcast_arrays(*(np.asarray(c, np.uint64) & m for c in (c0, c1, c2, c3)))
+    k0, k1 = np.uint64(int(seed) & M32), np.uint64((int(seed) >> 32) & M32)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & m, (p0 >> s32) ^ c3 ^ k1, p0 & m
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m, (k1 + np.uint64(0xBB67AE85)) & m
+    return np.stack([c0, c1, c2, c3], -1).astype(np.uint32)
+
+
+def u01_v(x):
+    """``u01`` on arrays."""
+    return (np.asarray(x, np.uint32) >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+
+
+def policy_normals_rows(grows, counter, seed, na):
+    """``policy_normals`` of many rows at once through ``philox_v``: float64 (normals [rows, na], rad [rows, na])."""
+    c1, c2 = step_key(RNG_POLICY, counter)
+    j = np.arange(na)
+    w = philox_v(np.asarray(grows, np.int64)[:, None] & M32, c1, c2, (j >> 1)[None, :], seed)
+    return box_muller(u01_v(w[..., 0]), u01_v(w[..., 1]), ((j & 1) == 1)[None, :])
 
 
 # ---------------------------------------------------------------------------------------------------------------
