@@ -1061,68 +1061,9 @@ __global__ void pad_cols_kernel(const float* __restrict__ W, int rows, int h, in
   }
 }
 
-// host side: workspace plan
-struct Plan {
-  int B;
-  float *xa, *he1, *he2, *h1, *h2, *h3, *dh3, *dh2, *dh1, *dlat, *dhe2, *dhe1;
-  float *tgt, *hd1, *hd2, *dhd2, *dhd1;
-  float* wd1p;     // adaptation layer-1 weights at the padded history pitch (zero columns past num_hist)
-  float* part;     // partial area (reused by phases 1 and 3)
-  int64_t part_floats;
-  uint16_t* wpl;   // pre-split weight planes (x6p products): the caller's jobs, built once per call
-  int64_t bytes;
-};
-
-// The weight products of the update that run on the x6p kernel (pre-split B, csrc/lrl_gemm.hip): their planes are
-// split from the current parameters at the start of each forward_backward / adaptation call (one launch).
-enum MainPlane { PL_W1, PL_W2, PL_W3, PL_E2, PL_W2T, PL_W3T, PL_E2T, PL_MAIN };
-enum AdaptPlane { PL_D1, PL_AE2, PL_D2T, PL_ADAPT };
-static int hist_pad(int h);
-static int xs_of(const lrl_ppo_net& n);
-// main: forward W1 (k padded to X's pitch), W2, W3, the encoder's W2; backward-data W2^T, W3^T, encoder W2^T
-static void main_plane_jobs(const lrl_ppo_net& n, const float* w, uint16_t* base, PlaneJob (&j)[PL_MAIN]) {
-  const int h0 = n.ac_h0, h1 = n.ac_h1, h2 = n.ac_h2, nx = n.num_obs + n.latent;
-  auto set = [&](PlaneJob& q, int64_t off, int rows, int cols, int64_t ldw, int trans, int groups, int64_t gsrc) {
-    q.W = w ? w + off : nullptr; q.rows = rows; q.cols = cols; q.ldw = ldw; q.trans = trans; q.groups = groups;
-    q.gsrc = gsrc;
-  };
-  set(j[PL_W1], n.w1, 2 * h0, nx, nx, 0, 1, 0);
-  set(j[PL_W2], n.w2, h1, h0, h0, 0, 2, (int64_t)h1 * h0);
-  set(j[PL_W3], n.w3, h2, h1, h1, 0, 2, (int64_t)h2 * h1);
-  set(j[PL_E2], n.e2w, n.enc_h1, n.enc_h0, n.enc_h0, 0, 1, 0);
-  set(j[PL_W2T], n.w2, h1, h0, h0, 1, 2, (int64_t)h1 * h0);
-  set(j[PL_W3T], n.w3, h2, h1, h1, 1, 2, (int64_t)h2 * h1);
-  set(j[PL_E2T], n.e2w, n.enc_h1, n.enc_h0, n.enc_h0, 1, 1, 0);
-  int64_t off = 0;
-  for (auto& q : j) {
-    q.dst = base ? base + off : nullptr;
-    off += (plane_elems(q) + 127) / 128 * 128;
-  }
-}
-// adaptation: forward Wd1 (k padded to the history pitch), the encoder-target W2 (from `we`), backward-data Wd2^T
-static void adapt_plane_jobs(const lrl_ppo_net& n, const float* w, const float* we, uint16_t* base,
-                             PlaneJob (&j)[PL_ADAPT]) {
-  auto set = [&](PlaneJob& q, const float* src, int rows, int cols, int64_t ldw, int trans) {
-    q.W = src; q.rows = rows; q.cols = cols; q.ldw = ldw; q.trans = trans; q.groups = 1; q.gsrc = 0;
-  };
-  set(j[PL_D1], w ? w + n.d1w : nullptr, n.ad_h0, n.num_hist, n.num_hist, 0);
-  set(j[PL_AE2], we ? we + n.e2w : nullptr, n.enc_h1, n.enc_h0, n.enc_h0, 0);
-  set(j[PL_D2T], w ? w + n.d2w : nullptr, n.ad_h1, n.ad_h0, n.ad_h0, 1);
-  int64_t off = 0;
-  for (auto& q : j) {
-    q.dst = base ? base + off : nullptr;
-    off += (plane_elems(q) + 127) / 128 * 128;
-  }
-}
-static int64_t plane_area_elems(const lrl_ppo_net& n) {
-  PlaneJob a[PL_MAIN], b[PL_ADAPT];
-  main_plane_jobs(n, nullptr, nullptr, a);
-  adapt_plane_jobs(n, nullptr, nullptr, nullptr, b);
-  int64_t m = 0, d = 0;
-  for (auto& q : a) m += (plane_elems(q) + 127) / 128 * 128;
-  for (auto& q : b) d += (plane_elems(q) + 127) / 128 * 128;
-  return std::max(m, d);
-}
+// ---------------------------------------------------------------------------------------------------
+// host side: the network as a list of linear layers, the workspace plans, the GEMM helper that speaks layers, and the
+// forward chains the entry points below are made of
 
 // X = [obs | latent] row pitch: 64 for the blind policies (42 + 18), else rounded up to 16 floats (a height-scan
 // policy: 235 + 18 -> 256).  Columns nx..XS-1 are zero.
@@ -1133,69 +1074,217 @@ static int xs_of(const lrl_ppo_net& n) {
 }
 constexpr int LATS = 32;    // latent-wide buffers pitch
 constexpr int HD2S = 32;    // adaptation hidden-2 pitch
-
 static int hist_pad(int h) { return (h + 15) / 16 * 16; }
 
-static int64_t tn_part_floats(int M, int N, int K, int groups) {
-  const int s = gemm_pick_splits(M, N, K, groups);
-  return (int64_t)s * groups * ((int64_t)M * N + M);
+// The weight products that run on the x6p kernel (pre-split B, csrc/lrl_gemm.hip): their planes are split from the
+// current parameters at the start of each call (one launch).
+// main: forward W1 (k padded to X's pitch), W2, W3, the encoder's W2; backward-data W2^T, W3^T, encoder W2^T (the
+// rollout act takes the forward ones, PL_W1 .. PL_E2)
+enum MainPlane { PL_W1, PL_W2, PL_W3, PL_E2, PL_W2T, PL_W3T, PL_E2T, PL_MAIN };
+constexpr int PL_FWD = PL_E2 + 1;
+// adaptation: forward Wd1 (k padded to the history pitch), the encoder-target W2, backward-data Wd2^T
+enum AdaptPlane { PL_D1, PL_AE2, PL_D2T, PL_ADAPT };
+
+// One linear layer y = x W^T + b, `groups` independent problems side by side: group g reads the input's columns from
+// g * in, writes the output's from g * out, and its weights / biases lie out * ldw / out floats behind the previous.
+struct Layer {
+  int64_t w, b;  // offsets of W [groups][out][ldw] and b [groups][out] in the parameter (and gradient) buffer
+  int out, in;   // per group
+  int64_t ldw;   // row pitch of W
+  int kf;        // the forward's k extent: `in`, or the input's zero-padded width
+  int groups;
+  int fwd, bwd;  // the plane images of W / W^T among the chain's plane jobs (MainPlane, AdaptPlane), -1: none
+};
+static Layer layer(int64_t w, int64_t b, int out, int in, int groups = 1, int fwd = -1, int bwd = -1) {
+  return Layer{w, b, out, in, in, in, groups, fwd, bwd};
+}
+struct Net {
+  Layer enc[3];   // env-factor encoder, priv -> latent
+  Layer body[3];  // [actor; critic] bodies over X = [obs | latent], grouped (actor_only: the actor's half, one group)
+  Layer ad[3];    // adaptation module, history -> latent
+  Layer tgt[3];   // the encoder as the adaptation's target: its W2 planes are the adaptation set's
+  Layer mean;     // the actor's head as a layer (the student act)
+  Layer dlat;     // body 1 over X's latent columns alone: its backward-data product is the latent's gradient
+};
+static Net layers_of(const lrl_ppo_net& n, bool actor_only = false) {
+  Net L{};
+  const int g = actor_only ? 1 : 2;
+  // body 1's k runs over all XS columns of X: columns nx..XS-1 are zero, so the extra products (with the next row's
+  // first weights, or the first biases after the last row — finite values; zero planes on the x6p path) add exactly 0,
+  // and the product takes the unguarded float4 path
+  L.body[0] = layer(n.w1, n.b1, g * n.ac_h0, n.num_obs + n.latent, 1, PL_W1);
+  L.body[0].kf = xs_of(n);
+  L.body[1] = layer(n.w2, n.b2, n.ac_h1, n.ac_h0, g, PL_W2, PL_W2T);
+  L.body[2] = layer(n.w3, n.b3, n.ac_h2, n.ac_h1, g, PL_W3, PL_W3T);
+  L.mean = layer(n.w4a, n.b4a, n.num_actions, n.ac_h2);
+  if (n.plain) return L;  // no encoder, latent or adaptation module
+  L.enc[0] = layer(n.e1w, n.e1b, n.enc_h0, n.num_priv);
+  L.enc[1] = layer(n.e2w, n.e2b, n.enc_h1, n.enc_h0, 1, PL_E2, PL_E2T);
+  L.enc[2] = layer(n.e3w, n.e3b, n.latent, n.enc_h1);
+  for (int i = 0; i < 3; ++i) L.tgt[i] = L.enc[i];
+  L.tgt[1].fwd = PL_AE2;
+  L.tgt[1].bwd = -1;
+  L.ad[0] = layer(n.d1w, n.d1b, n.ad_h0, n.num_hist, 1, PL_D1);
+  L.ad[1] = layer(n.d2w, n.d2b, n.ad_h1, n.ad_h0, 1, -1, PL_D2T);
+  L.ad[2] = layer(n.d3w, n.d3b, n.latent, n.ad_h1);
+  // d latent = dH1 [W1a; W1c][:, num_obs:]  (sum over actor and critic halves: one reduction of length 2*h0)
+  L.dlat = L.body[0];
+  L.dlat.w += n.num_obs;
+  L.dlat.in = n.latent;
+  L.dlat.bwd = -1;
+  return L;
+}
+
+// The planes of one product's B operand as gemm_launch takes it: B [N][K] (NT) or [K][N] (NN) at pitch ldb, group
+// g's gb floats on.
+static PlaneJob plane_job(const float* B, int64_t ldb, int layout, int N, int K, int groups, int64_t gb) {
+  PlaneJob j{};
+  j.W = B; j.ldw = ldb; j.gsrc = gb; j.groups = groups; j.trans = layout == GEMM_NN ? 1 : 0;
+  j.rows = j.trans ? K : N; j.cols = j.trans ? N : K;
+  return j;
+}
+// a layer's forward and backward-data images, into their slots of j
+static void layer_planes(const Layer& l, const float* w, PlaneJob* j) {
+  const float* W = w ? w + l.w : nullptr;
+  const int64_t gb = l.groups > 1 ? l.out * l.ldw : 0;
+  if (l.fwd >= 0) j[l.fwd] = plane_job(W, l.ldw, GEMM_NT, l.out, l.in, l.groups, gb);
+  if (l.bwd >= 0) j[l.bwd] = plane_job(W, l.ldw, GEMM_NN, l.in, l.out, l.groups, gb);
+}
+// lay the jobs' planes one behind the other from base; returns their length in elements
+static int64_t place_planes(PlaneJob* j, int n, uint16_t* base) {
+  int64_t off = 0;
+  for (int i = 0; i < n; ++i) {
+    j[i].dst = base ? base + off : nullptr;
+    off += (plane_elems(j[i]) + 127) / 128 * 128;
+  }
+  return off;
+}
+static int64_t main_plane_jobs(const lrl_ppo_net& n, const float* w, uint16_t* base, PlaneJob (&j)[PL_MAIN]) {
+  const Net L = layers_of(n);
+  for (auto& l : L.enc) layer_planes(l, w, j);
+  for (auto& l : L.body) layer_planes(l, w, j);
+  return place_planes(j, PL_MAIN, base);
+}
+// (the target encoder's weights come from `we`)
+static int64_t adapt_plane_jobs(const lrl_ppo_net& n, const float* w, const float* we, uint16_t* base,
+                                PlaneJob (&j)[PL_ADAPT]) {
+  const Net L = layers_of(n);
+  for (auto& l : L.ad) layer_planes(l, w, j);
+  for (auto& l : L.tgt) layer_planes(l, we, j);
+  return place_planes(j, PL_ADAPT, base);
+}
+
+// An activation buffer: rows at a pitch.  In is a read-only one (the caller's inputs).
+struct In { const float* p; int64_t ld; };
+struct Buf { float* p; int64_t ld; operator In() const { return In{p, ld}; } };
+static Buf cols_from(Buf b, int col) { return Buf{b.p ? b.p + col : nullptr, b.ld}; }
+
+// workspace carver: every buffer starts on a 256-byte boundary (base == nullptr: sizes only)
+struct Arena {
+  char* base;
+  int64_t off = 0;
+  float* take(int64_t floats) {
+    float* r = base ? reinterpret_cast<float*>(base + off) : nullptr;
+    off += ((floats * 4 + 255) / 256) * 256;
+    return r;
+  }
+  Buf take(int64_t rows, int64_t ld) { return Buf{take(rows * ld), ld}; }
+};
+
+// The workspace of the update and adaptation calls (make_plan), of the rollout act (make_act_plan: the forward
+// buffers and the forward planes) and of the student act (make_student_plan); a buffer a form does not have is null.
+struct Plan {
+  Buf xa, he1, he2, h1, h2, h3, dh3, dh2, dh1, dlat, dhe2, dhe1;
+  Buf tgt, hd1, hd2, dhd2, dhd1;
+  Buf wd1p;        // adaptation layer-1 weights at the padded history pitch (zero columns past num_hist)
+  float* part;     // partial area (reused by phases 1 and 3)
+  int64_t part_floats;
+  uint16_t* wpl;   // pre-split weight planes (x6p products): the caller's jobs, built once per call
+  int64_t bytes;
+};
+
+static int64_t splitk_floats(int M, int N, int splits, int groups) { return (int64_t)splits * groups * ((int64_t)M * N + M); }
+static int64_t part_floats_of(const Layer& l, int B) {
+  return splitk_floats(l.out, l.in, gemm_pick_splits(l.out, l.in, B, l.groups), l.groups);
+}
+
+// X, the encoder's hidden layers (not for a plain net) and the bodies' three, `bw` body halves wide
+static void take_forward(Arena& a, Plan& p, const lrl_ppo_net& n, int64_t R, int bw) {
+  p.xa = a.take(R, xs_of(n));
+  if (!n.plain) {
+    p.he1 = a.take(R, n.enc_h0);
+    p.he2 = a.take(R, n.enc_h1);
+  }
+  p.h1 = a.take(R, bw * n.ac_h0);
+  p.h2 = a.take(R, bw * n.ac_h1);
+  p.h3 = a.take(R, bw * n.ac_h2);
 }
 
 static Plan make_plan(const lrl_ppo_net& n, int B, char* base) {
   Plan p{};
-  p.B = B;
-  int64_t off = 0;
-  auto take = [&](int64_t floats) {
-    float* r = base ? reinterpret_cast<float*>(base + off) : nullptr;
-    off += ((floats * 4 + 255) / 256) * 256;
-    return r;
-  };
-  const int64_t Bl = B;
-  if (n.plain) {  // actor / critic bodies over the observations alone: no encoder, latent or adaptation buffers
-    p.xa = take(Bl * xs_of(n));
-    p.h1 = take(Bl * 2 * n.ac_h0);
-    p.h2 = take(Bl * 2 * n.ac_h1);
-    p.h3 = take(Bl * 2 * n.ac_h2);
-    p.dh3 = take(Bl * 2 * n.ac_h2);
-    p.dh2 = take(Bl * 2 * n.ac_h1);
-    p.dh1 = take(Bl * 2 * n.ac_h0);
-    const int hbp = (B + HEAD_ROWS - 1) / HEAD_ROWS;
-    // (64 * 8 floats of slack: the head's slice and each product's cursor are rounded up to 64 floats)
-    p.part_floats = tn_part_floats(n.ac_h2, n.ac_h1, B, 2) + tn_part_floats(n.ac_h1, n.ac_h0, B, 2) +
-                    tn_part_floats(2 * n.ac_h0, n.num_obs, B, 1) + (int64_t)hbp * hp_len(n.num_actions) + 64 * 8;
-    p.part = take(p.part_floats);
-    p.bytes = off;
-    return p;
-  }
-  p.xa = take(Bl * xs_of(n));
-  p.he1 = take(Bl * n.enc_h0);
-  p.he2 = take(Bl * n.enc_h1);
-  p.h1 = take(Bl * 2 * n.ac_h0);
-  p.h2 = take(Bl * 2 * n.ac_h1);
-  p.h3 = take(Bl * 2 * n.ac_h2);
-  p.dh3 = take(Bl * 2 * n.ac_h2);
-  p.dh2 = take(Bl * 2 * n.ac_h1);
-  p.dh1 = take(Bl * 2 * n.ac_h0);
-  p.dlat = take(Bl * LATS);
-  p.dhe2 = take(Bl * n.enc_h1);
-  p.dhe1 = take(Bl * n.enc_h0);
-  p.tgt = take(Bl * LATS);
-  p.hd1 = take(Bl * n.ad_h0);
-  p.hd2 = take(Bl * HD2S);
-  p.dhd2 = take(Bl * HD2S);
-  p.dhd1 = take(Bl * n.ad_h0);
-  p.wd1p = take((int64_t)n.ad_h0 * hist_pad(n.num_hist));
+  Arena a{base};
+  const Net L = layers_of(n);
+  take_forward(a, p, n, B, 2);
+  p.dh3 = a.take(B, 2 * n.ac_h2);
+  p.dh2 = a.take(B, 2 * n.ac_h1);
+  p.dh1 = a.take(B, 2 * n.ac_h0);
   const int hb = (B + HEAD_ROWS - 1) / HEAD_ROWS;
-  int64_t ph1 = tn_part_floats(n.ac_h2, n.ac_h1, B, 2) + tn_part_floats(n.ac_h1, n.ac_h0, B, 2) +
-                tn_part_floats(2 * n.ac_h0, n.num_obs + n.latent, B, 1) + tn_part_floats(n.latent, n.enc_h1, B, 1) +
-                tn_part_floats(n.enc_h1, n.enc_h0, B, 1) + tn_part_floats(n.enc_h0, n.num_priv, B, 1) +
+  // (64 * 8 floats of slack: the head's slice and each product's cursor are rounded up to 64 floats)
+  int64_t ph1 = part_floats_of(L.body[2], B) + part_floats_of(L.body[1], B) + part_floats_of(L.body[0], B) +
                 (int64_t)hb * hp_len(n.num_actions) + 64 * 8;
-  int64_t ph3 = tn_part_floats(n.ad_h1, n.ad_h0, B, 1) + tn_part_floats(n.ad_h0, n.num_hist, B, 1) +
-                (int64_t)hb * (n.latent * n.ad_h1 + n.latent + 1) + 64 * 4;
+  int64_t ph3 = 0;
+  if (!n.plain) {
+    p.dlat = a.take(B, LATS);
+    p.dhe2 = a.take(B, n.enc_h1);
+    p.dhe1 = a.take(B, n.enc_h0);
+    p.tgt = a.take(B, LATS);
+    p.hd1 = a.take(B, n.ad_h0);
+    p.hd2 = a.take(B, HD2S);
+    p.dhd2 = a.take(B, HD2S);
+    p.dhd1 = a.take(B, n.ad_h0);
+    p.wd1p = a.take(n.ad_h0, hist_pad(n.num_hist));
+    ph1 += part_floats_of(L.enc[2], B) + part_floats_of(L.enc[1], B) + part_floats_of(L.enc[0], B);
+    ph3 = part_floats_of(L.ad[1], B) + part_floats_of(L.ad[0], B) +
+          (int64_t)hb * (n.latent * n.ad_h1 + n.latent + 1) + 64 * 4;
+  }
   p.part_floats = std::max(ph1, ph3);
-  p.part = take(p.part_floats);
-  p.wpl = reinterpret_cast<uint16_t*>(take((plane_area_elems(n) + 1) / 2));
-  p.bytes = off;
+  p.part = a.take(p.part_floats);
+  if (!n.plain) {
+    PlaneJob m[PL_MAIN], d[PL_ADAPT];
+    const int64_t elems = std::max(main_plane_jobs(n, nullptr, nullptr, m), adapt_plane_jobs(n, nullptr, nullptr, nullptr, d));
+    p.wpl = reinterpret_cast<uint16_t*>(a.take((elems + 1) / 2));
+  }
+  p.bytes = a.off;
+  return p;
+}
+
+// rollout forward workspace: X [n][XS], HE1, HE2, H1 [n][2 h0], H2, H3, the forward weight planes (LRL_ACT_PLANES=1:
+// the x6p kernel for the act's weight products)
+static Plan make_act_plan(const lrl_ppo_net& n, int rows, char* base) {
+  Plan p{};
+  Arena a{base};
+  take_forward(a, p, n, rows, 2);
+  if (!n.plain) {
+    PlaneJob j[PL_MAIN];
+    main_plane_jobs(n, nullptr, nullptr, j);
+    p.wpl = reinterpret_cast<uint16_t*>(a.take((place_planes(j, PL_FWD, nullptr) + 1) / 2));
+  }
+  p.bytes = a.off;
+  return p;
+}
+
+// student act: X, the adaptation module's hidden layers, the actor's half of the bodies, the padded Wd1
+static Plan make_student_plan(const lrl_ppo_net& n, int rows, char* base) {
+  Plan p{};
+  Arena a{base};
+  p.xa = a.take(rows, xs_of(n));
+  p.hd1 = a.take(rows, n.ad_h0);
+  p.hd2 = a.take(rows, HD2S);
+  p.h1 = a.take(rows, n.ac_h0);
+  p.h2 = a.take(rows, n.ac_h1);
+  p.h3 = a.take(rows, n.ac_h2);
+  p.wd1p = a.take(n.ad_h0, hist_pad(n.num_hist));
+  p.bytes = a.off;
   return p;
 }
 
@@ -1221,10 +1310,8 @@ static int check_net(const lrl_ppo_net* n) {
   return 0;
 }
 
-static void launch_seg(const SegList& L, hipStream_t st);
-
 // Optional timing of the update's largest product (the actor/critic layer-2 weight gradient, 2 x 256x512
-// over the minibatch rows): HIP events around that launch on its stream, read back by lrl_ppo_timing_read.
+// over the minibatch rows): HIP events around that launch on its stream, read back by lrl_ppo_timing.
 struct GemmTimer {
   bool on = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
@@ -1248,85 +1335,94 @@ static void timer_end(hipStream_t st) {
   if (pr.second) (void)hipEventRecord(pr.second, st);
 }
 
-// one GEMM helper per layout
+// A weight gradient dW[g][m][n] = sum_k dY[k][m] X[rows(k)][n] as a split-k product and its reduction: partials
+// [split][group][M][N] at `part`, the bias gradient's [split][group][M] (column sums of dY) behind them, one segment
+// each into dw and db.  Group g's operands start gy / gx floats on; splits == 0: gemm_pick_splits' count.
+struct SplitK { GemmP p; Seg s[2]; };  // (weights' segment, biases')
+// False, and nothing set, when the partials would pass `end`; else `part` moves behind them.
+static bool splitk_job(int M, int N, int K, int groups, int splits, In dY, int64_t gy, In X, int64_t gx,
+                       const int64_t* rows, float* dw, float* db, float*& part, const float* end, SplitK& o) {
+  if (!splits) splits = gemm_pick_splits(M, N, K, groups);
+  const int64_t gmn = (int64_t)groups * M * N, gm = (int64_t)groups * M;
+  if (splitk_floats(M, N, splits, groups) > end - part) return false;
+  GemmP p{};
+  p.A = dY.p; p.lda = dY.ld; p.ga = gy; p.B = X.p; p.ldb = X.ld; p.gb = gx; p.b_rows = rows;
+  p.M = M; p.N = N; p.K = K; p.splits = splits; p.kps = (K + splits - 1) / splits;
+  p.gc = (int64_t)M * N; p.ldc = N; p.part_stride = gmn;
+  p.C = part;
+  p.bias_part = part + splits * gmn;
+  o.p = p;
+  o.s[0] = Seg{part, dw, gmn, gmn, splits, 1.f};
+  o.s[1] = Seg{p.bias_part, db, gm, gm, splits, 1.f};
+  part = p.bias_part + splits * gm;
+  return true;
+}
+
+// The products of a call, layer by layer: launched on `st` as they are named, or, after collect(), appended to the
+// caller's job list (as gemm_launch would receive them) for it to launch alone or packed (launch_jobs); everything
+// else the helpers do stays the same.
 struct G {
   hipStream_t st;
-  float* part_end;  // end of the partial area: a product that would not fit is refused before launch
+  const float* w;  // the parameters the layers' offsets point into
+  int m;           // rows of every product's batch dimension
+  float* part = nullptr;      // cursor in the partial area: the next weight gradient's partials
+  float* part_end = nullptr;  // its end: a product that would not fit is refused before launch
   int rc = 0;
-  const PlaneJob* pl = nullptr;  // pre-split B of the next nt / nn product (consumed by it)
-  bool tanh_act = false;         // the activation epilogues: tanh / 1 - y^2 instead of ELU / elu'
-  G& with(const PlaneJob& j) {
-    pl = &j;
-    return *this;
-  }
-  void take_planes(GemmP& p) {
-    if (pl) gemm_use_planes(p, *pl);
-    pl = nullptr;
-  }
-  // collect, don't launch: with `jobs` set, every product is appended there (as gemm_launch would receive it) for the
-  // caller to launch, alone or as a multi-problem launch (launch_jobs); everything else the helpers do stays the same
+  const PlaneJob* planes = nullptr;  // the chain's plane jobs: a layer with an image there runs on it
+  bool tanh_act = false;             // the activation epilogues: tanh / 1 - y^2 instead of ELU / elu'
   GemmJob* jobs = nullptr;
   int njobs = 0, max_jobs = 0;
-  void launch(const GemmP& p, int layout, int epi, int groups) {
+  void with(const PlaneJob* chain) { planes = chain; }
+  void collect(GemmJob* list, int first, int max) { jobs = list; njobs = first; max_jobs = max; }  // next: list[first]
+  void launch(GemmP& p, int image, int layout, int epi, int groups) {
+    if (planes && image >= 0) gemm_use_planes(p, planes[image]);
     if (!jobs) rc = gemm_launch(p, layout, epi, groups, st);
     else if (njobs < max_jobs) jobs[njobs++] = GemmJob{p, layout, epi, groups};
     else rc = LRL_E_INVALID;
   }
-  void nt(const float* A, int64_t lda, const int64_t* rows, const float* W, int64_t ldw, float* C, int64_t ldc,
-          const float* bias, int M, int N, int K, bool elu, int groups = 1, int64_t ga = 0, int64_t gw = 0,
-          int64_t gc = 0, int64_t gbias = 0) {
+  // y = act(x[rows] W^T + b); W read from `Wsub` where given (a re-pitched copy) instead of the parameters
+  void forward(const Layer& l, In x, const int64_t* rows, Buf y, bool act, const float* Wsub = nullptr) {
     if (rc) return;
     GemmP p{};
-    p.A = A; p.lda = lda; p.a_rows = rows; p.B = W; p.ldb = ldw; p.C = C; p.ldc = ldc; p.bias = bias;
-    p.M = M; p.N = N; p.K = K; p.splits = 1;
-    p.ga = ga; p.gb = gw; p.gc = gc; p.gbias = gbias;
-    take_planes(p);
-    launch(p, GEMM_NT, elu ? (tanh_act ? EPI_BIAS_TANH : EPI_BIAS_ELU) : EPI_BIAS, groups);
+    p.A = x.p; p.lda = x.ld; p.a_rows = rows; p.B = Wsub ? Wsub : w + l.w; p.ldb = l.ldw; p.C = y.p; p.ldc = y.ld;
+    p.bias = w + l.b;
+    p.M = m; p.N = l.out; p.K = l.kf; p.splits = 1;
+    if (l.groups > 1) { p.ga = l.in; p.gb = l.out * l.ldw; p.gc = l.out; p.gbias = l.out; }
+    launch(p, l.fwd, GEMM_NT, act ? (tanh_act ? EPI_BIAS_TANH : EPI_BIAS_ELU) : EPI_BIAS, l.groups);
   }
-  // dX = dY W (* elu'(aux) if aux)
-  void nn(const float* dY, int64_t ldy, const float* W, int64_t ldw, float* dX, int64_t ldx, const float* aux,
-          int64_t ldaux, int M, int N, int K, int groups = 1, int64_t gy = 0, int64_t gw = 0, int64_t gx = 0,
-          int64_t gaux = 0) {
+  // dX = dY W (* act'(aux) where aux, the layer's activated input, is given)
+  void backward_data(const Layer& l, In dY, Buf dX, In aux) {
     if (rc) return;
     GemmP p{};
-    p.A = dY; p.lda = ldy; p.B = W; p.ldb = ldw; p.C = dX; p.ldc = ldx; p.aux = aux; p.ld_aux = ldaux;
-    p.M = M; p.N = N; p.K = K; p.splits = 1;
-    p.ga = gy; p.gb = gw; p.gc = gx; p.gaux = gaux;
-    take_planes(p);
-    launch(p, GEMM_NN, aux ? (tanh_act ? EPI_DTANH : EPI_DELU) : EPI_STORE, groups);
+    p.A = dY.p; p.lda = dY.ld; p.B = w + l.w; p.ldb = l.ldw; p.C = dX.p; p.ldc = dX.ld; p.aux = aux.p; p.ld_aux = aux.ld;
+    p.M = m; p.N = l.in; p.K = l.out; p.splits = 1;
+    if (l.groups > 1) { p.ga = l.out; p.gb = l.out * l.ldw; p.gc = l.in; p.gaux = l.in; }
+    launch(p, l.bwd, GEMM_NN, aux.p ? (tanh_act ? EPI_DTANH : EPI_DELU) : EPI_STORE, l.groups);
   }
-  // partial dW[o][i] = sum_b dY[b][o] X[rows(b)][i]; returns the segments (weights then biases)
-  void tn(const float* dY, int64_t ldy, const float* X, int64_t ldx, const int64_t* rows, int M, int N, int K,
-          int groups, int64_t gy, int64_t gx, float*& part, float* dw, float* db, SegList& L) {
+  // partial dW[o][i] = sum_b dY[b][o] X[rows(b)][i] at the cursor; its segments (weights then biases) go to L
+  void weight_grad(const Layer& l, In dY, In X, const int64_t* rows, float* grads, SegList& L) {
     if (rc) return;
-    const int splits = gemm_pick_splits(M, N, K, groups);
-    if (part + (int64_t)splits * groups * ((int64_t)M * N + M) > part_end) { rc = LRL_E_INVALID; return; }
-    GemmP p{};
-    p.A = dY; p.lda = ldy; p.B = X; p.ldb = ldx; p.b_rows = rows;
-    p.M = M; p.N = N; p.K = K; p.splits = splits; p.kps = (K + splits - 1) / splits;
-    p.ga = gy; p.gb = gx; p.gc = (int64_t)M * N; p.ldc = N;
-    p.part_stride = (int64_t)groups * M * N;
-    p.C = part;
-    p.bias_part = part + (int64_t)splits * groups * M * N;
-    launch(p, GEMM_TN, EPI_PARTIAL, groups);
+    const bool grouped = l.groups > 1;
+    SplitK k;
+    if (L.n + 2 > MAX_SEGS || !splitk_job(l.out, l.in, m, l.groups, 0, dY, grouped ? l.out : 0, X, grouped ? l.in : 0,
+                                          rows, grads + l.w, grads + l.b, part, part_end, k)) {
+      rc = LRL_E_INVALID;
+      return;
+    }
+    launch(k.p, -1, GEMM_TN, EPI_PARTIAL, l.groups);
     if (rc) return;
-    if (L.n + 2 > MAX_SEGS) { rc = LRL_E_INVALID; return; }
-    L.s[L.n++] = Seg{part, dw, (int64_t)groups * M * N, (int64_t)groups * M * N, splits, 1.f};
-    L.s[L.n++] = Seg{p.bias_part, db, (int64_t)groups * M, (int64_t)groups * M, splits, 1.f};
-    part = p.bias_part + (int64_t)splits * groups * M;
+    L.s[L.n++] = k.s[0];
+    L.s[L.n++] = k.s[1];
     part = reinterpret_cast<float*>(((reinterpret_cast<uintptr_t>(part) + 255) / 256) * 256);
   }
 };
 
 // Launch the collected jobs all[idx[0 .. n)] in that order: as one multi-problem launch where the set is one that
 // gemm_launch_multi offers, one by one otherwise (other widths, the fp32 paths of lrl_debug_gemm_paths, LRL_GEMM_X6=0).
-static int launch_jobs(const GemmJob* all, std::initializer_list<int> idx, hipStream_t st) {
+static int launch_jobs(const GemmJob* all, const int* idx, int n, hipStream_t st) {
   GemmJob js[MAX_MULTI_JOBS];
-  int n = 0;
-  for (int i : idx) {
-    if (n == MAX_MULTI_JOBS) return LRL_E_INVALID;
-    js[n++] = all[i];
-  }
+  if (n > MAX_MULTI_JOBS) return LRL_E_INVALID;
+  for (int i = 0; i < n; ++i) js[i] = all[idx[i]];
   if (n > 1) {
     const int r = gemm_launch_multi(js, n, st);
     if (r) return r < 0 ? r : 0;
@@ -1336,8 +1432,8 @@ static int launch_jobs(const GemmJob* all, std::initializer_list<int> idx, hipSt
   return 0;
 }
 
-// How the backward tail of lrl_ppo_forward_backward packs its eight products, LRL_PPO_BWD_MULTI read at every call (a
-// test flips it in one process): 1 (default) = three multi-problem launches on the caller's stream, the encoder's
+// How the backward tail of lrl_ppo_forward_backward launches its eight products, LRL_PPO_BWD_MULTI read at every call
+// (a test flips it in one process): 1 (default) = three multi-problem launches on the caller's stream, the encoder's
 // products riding in front of the weight gradients' workgroups — {dWe3, dhe2 | dW3}, {dWe2, dhe1 | dW1}, {dWe1 | dW2};
 // 2 and 3 = the same riders on other hosts (measurement switches: dW3, dW2, dW1 and dW2, dW1, dW3); 0 = eight
 // launches, the encoder's chain forked to the library's second stream (below).  Every setting gives the same bits.
@@ -1408,78 +1504,92 @@ static void launch_seg(const SegList& L0, hipStream_t st) {
   if (total > 0) hipLaunchKernelGGL(seg_reduce_kernel, dim3(total), dim3(256), 0, st, L);
 }
 
+// Split the first n jobs' matrices into their planes where `on` (one launch); else no job of the chain has planes and
+// every product reads its fp32 B
+template <int NJ>
+static int split_planes(PlaneJob (&j)[NJ], int n, bool on, hipStream_t st) {
+  if (on) return x6_planes_launch(j, n, st);
+  for (auto& q : j) q.dst = nullptr;
+  return 0;
+}
+
+// ---- the chains ----
+// X = [obs[rows] | 0]: the latent's columns are written by the encoder (or the adaptation module) behind it
+static void prep_x(const lrl_ppo_net& n, const float* obs, const int64_t* rows, int m, Buf xa, hipStream_t st) {
+  hipLaunchKernelGGL(ppo_prep_kernel, dim3(prep_blocks(m, (int)xa.ld)), dim3(256), 0, st, obs, rows, m, n.num_obs,
+                     (int)xa.ld, xa.p);
+}
+// latent = env_factor_encoder(priv[rows])
+static void encoder_forward(G& g, const Layer (&e)[3], In priv, const int64_t* rows, const Plan& P, Buf latent) {
+  g.forward(e[0], priv, rows, P.he1, true);
+  g.forward(e[1], P.he1, nullptr, P.he2, true);
+  g.forward(e[2], P.he2, nullptr, latent, false);
+}
+// H1, H2, H3 of the actor / critic bodies over X
+static void body_forward(G& g, const Layer (&b)[3], const Plan& P) {
+  g.forward(b[0], P.xa, nullptr, P.h1, true);
+  g.forward(b[1], P.h1, nullptr, P.h2, true);
+  g.forward(b[2], P.h2, nullptr, P.h3, true);
+}
+// hd1 = act(hist[rows] Wd1^T + b).  History rows that carry finite padding up to the 16-float pitch (and are float4
+// aligned) run k = hpad against zero-padded weights, so the product reads float4 rows
+static void adaptation_l1_forward(G& g, Layer l, In hist, const int64_t* rows, const Plan& P) {
+  const int h = l.in, hpad = hist_pad(h);
+  if (hist.ld >= hpad && hist.ld % 4 == 0 && ((uintptr_t)hist.p & 15) == 0 && hpad != h) {
+    const int64_t cnt = (int64_t)l.out * hpad;
+    hipLaunchKernelGGL(pad_cols_kernel, dim3((unsigned)std::min<int64_t>((cnt + 255) / 256, 1024)), dim3(256), 0, g.st,
+                       g.w + l.w, l.out, h, hpad, P.wd1p.p);
+    l.kf = hpad;
+    l.ldw = hpad;
+    g.forward(l, hist, rows, P.hd1, true, P.wd1p.p);
+  } else {
+    l.fwd = -1;
+    g.forward(l, hist, rows, P.hd1, true);
+  }
+}
+
+// The PPO loss head over H3 (dH3 and the per-workgroup partials of the head's gradients, the KL and the two losses)
+// and the segments that reduce those partials, from the cursor `part`
+static void launch_loss_head(const lrl_ppo_net& n, const float* w, float* grads, const lrl_ppo_batch* bt,
+                             const lrl_ppo_hparams* hp, lrl_ppo_ctrl* ctrl, const Plan& P, float*& part, SegList& L,
+                             hipStream_t st) {
+  const int B = bt->batch, na = n.num_actions, hb = (B + HEAD_ROWS - 1) / HEAD_ROWS;
+  HeadArgs ha{};
+  ha.h3 = P.h3.p; ha.dh3 = P.dh3.p;
+  ha.w4a = w + n.w4a; ha.b4a = w + n.b4a; ha.w4c = w + n.w4c; ha.b4c = w + n.b4c; ha.stdv = w + n.std_off;
+  ha.actions = bt->actions; ha.old_mu = bt->mu; ha.old_sigma = bt->sigma; ha.tv = bt->values; ha.ret = bt->returns;
+  ha.adv = bt->adv; ha.old_logp = bt->logp; ha.rows = bt->rows;
+  ha.B = B; ha.na = na; ha.clip = hp->clip_param; ha.ent_coef = hp->entropy_coef; ha.vcoef = hp->value_loss_coef;
+  ha.clipped_value = hp->use_clipped_value_loss;
+  ha.part = part; ha.part_len = hp_len(na);
+  if (n.plain && na == 3) hipLaunchKernelGGL((ppo_head_kernel<3, true>), dim3(hb), dim3(HEAD_THREADS), 0, st, ha);
+  else if (n.plain) hipLaunchKernelGGL((ppo_head_kernel<HEAD_NA, true>), dim3(hb), dim3(HEAD_THREADS), 0, st, ha);
+  else hipLaunchKernelGGL((ppo_head_kernel<HEAD_NA, false>), dim3(hb), dim3(HEAD_THREADS), 0, st, ha);
+  const int64_t pl = hp_len(na);
+  const float invB = 1.f / (float)B;
+  L.s[L.n++] = Seg{part + hp_w4a(na), grads + n.w4a, (int64_t)na * HEAD_W, pl, hb, 1.f};
+  L.s[L.n++] = Seg{part + hp_b4a(na), grads + n.b4a, na, pl, hb, 1.f};
+  L.s[L.n++] = Seg{part + hp_w4c(na), grads + n.w4c, HEAD_W, pl, hb, 1.f};
+  L.s[L.n++] = Seg{part + hp_b4c(na), grads + n.b4c, 1, pl, hb, 1.f};
+  L.s[L.n++] = Seg{part + hp_std(na), grads + n.std_off, na, pl, hb, 1.f};
+  L.s[L.n++] = Seg{part + hp_kl(na), grads + n.kl_slot, 1, pl, hb, invB};
+  L.s[L.n++] = Seg{part + hp_kl(na) + 1, &ctrl->mb[1], 1, pl, hb, invB};
+  L.s[L.n++] = Seg{part + hp_kl(na) + 2, &ctrl->mb[0], 1, pl, hb, invB};
+  part += ((hb * pl + 63) / 64) * 64;
+}
+
 }  // namespace lrl
 
 using namespace lrl;
 
-// rollout forward workspace: X [n][64], HE1, HE2, H1 [n][2 h0], H2, H3
-struct ActPlan {
-  float *xa, *he1, *he2, *h1, *h2, *h3;
-  uint16_t* wpl;  // forward weight planes (LRL_ACT_PLANES=1: the x6p kernel for the act's weight products)
-  int64_t bytes;
-};
-// the forward jobs of main_plane_jobs (PL_W1 .. PL_E2) are the act's weight products
-constexpr int PL_FWD = PL_E2 + 1;
 static bool act_planes_on() {
   const char* e = getenv("LRL_ACT_PLANES");  // (read per call: A/B timing in one process)
   return e && e[0] == '1' && gemm_x6p_enabled();
 }
-static ActPlan make_act_plan(const lrl_ppo_net& n, int rows, char* base) {
-  ActPlan p;
-  int64_t off = 0;
-  auto take = [&](int64_t floats) {
-    float* r = base ? reinterpret_cast<float*>(base + off) : nullptr;
-    off += ((floats * 4 + 255) / 256) * 256;
-    return r;
-  };
-  const int64_t R = rows;
-  if (n.plain) {  // X = [obs | 0] and the three hidden layers
-    p = ActPlan{};
-    p.xa = take(R * xs_of(n));
-    p.h1 = take(R * 2 * n.ac_h0);
-    p.h2 = take(R * 2 * n.ac_h1);
-    p.h3 = take(R * 2 * n.ac_h2);
-    p.bytes = off;
-    return p;
-  }
-  p.xa = take(R * xs_of(n));
-  p.he1 = take(R * n.enc_h0);
-  p.he2 = take(R * n.enc_h1);
-  p.h1 = take(R * 2 * n.ac_h0);
-  p.h2 = take(R * 2 * n.ac_h1);
-  p.h3 = take(R * 2 * n.ac_h2);
-  {
-    PlaneJob j[PL_MAIN];
-    main_plane_jobs(n, nullptr, nullptr, j);
-    int64_t e = 0;
-    for (int i = 0; i < PL_FWD; ++i) e += (plane_elems(j[i]) + 127) / 128 * 128;
-    p.wpl = reinterpret_cast<uint16_t*>(take((e + 1) / 2));
-  }
-  p.bytes = off;
-  return p;
-}
 
-// The fused act's envelope (LDS pitches, tile runs that never cross a group); LRL_ACT_FUSED=1 selects it over the GEMM chain
-// (A/B timing and the tests that compare the two)
-// the encoder part of act_fused_kernel in the rollout act's chain (LRL_ACT_ENC_FUSED=0: the prep kernel + three
-// GEMM launches instead; read per call so a test can switch it inside one process)
-static bool act_enc_fused(const lrl_ppo_net& n) {
-  const char* e = getenv("LRL_ACT_ENC_FUSED");
-  if (e && e[0] == '0') return false;
-  auto run_ok = [](int Ng) {
-    if (Ng % 16) return false;
-    const int T = Ng / 16, tpw = T >= 4 ? T / 4 : 1;
-    if (T >= 4 && T % 4) return false;
-    return T % std::min(tpw, 8) == 0;
-  };
-  return xs_of(n) % 32 == 0 && xs_of(n) <= 256 && n.num_priv <= 32 && n.enc_h0 <= 256 && n.enc_h0 % 32 == 0 &&
-         n.enc_h1 % 32 == 0 && n.enc_h1 + 4 <= FA_ENC_MIDP && n.latent <= 32 && run_ok(n.enc_h0) && run_ok(n.enc_h1) &&
-         run_ok((n.latent + 15) / 16 * 16);
-}
-
-static bool fused_act_fits(const lrl_ppo_net& n) {
-  const char* e = getenv("LRL_ACT_FUSED");  // (read per call: a test switches it inside one process)
-  if (!(e && e[0] == '1')) return false;  // off by default until it measures faster than the chain
+// The envelope of act_fused_kernel (LDS pitches, tile runs that never cross a group): of the whole act (`body`), or of
+// its encoder part alone, which writes X for the GEMM chain.
+static bool fused_envelope(const lrl_ppo_net& n, bool body) {
   auto run_ok = [](int groups, int Ng) {  // fa_layer: equal runs per wave inside one group
     if (Ng % 16) return false;
     const int T = groups * (Ng / 16), tpg = Ng / 16;
@@ -1487,11 +1597,41 @@ static bool fused_act_fits(const lrl_ppo_net& n) {
     if (T >= 4 && T % 4) return false;
     return tpg % std::min(tpw, 8) == 0;
   };
-  return xs_of(n) % 32 == 0 && n.enc_h0 % 32 == 0 && n.enc_h1 % 32 == 0 && n.ac_h0 % 32 == 0 && n.ac_h1 % 32 == 0 &&
-         n.num_priv <= 32 && n.enc_h0 <= 256 && n.enc_h1 + 4 <= FA_MIDP && n.latent <= 32 && xs_of(n) <= 256 &&
-         2 * n.ac_h0 <= 1024 && 2 * n.ac_h1 <= 512 && 2 * n.ac_h2 <= 256 && n.enc_h0 % 16 == 0 && n.enc_h1 % 16 == 0 &&
-         n.ac_h0 % 16 == 0 && n.ac_h1 % 16 == 0 && run_ok(1, n.enc_h0) && run_ok(1, n.enc_h1) &&
-         run_ok(1, (n.latent + 15) / 16 * 16) && run_ok(1, 2 * n.ac_h0) && run_ok(2, n.ac_h1) && run_ok(2, n.ac_h2);
+  if (!(xs_of(n) % 32 == 0 && xs_of(n) <= 256 && n.num_priv <= 32 && n.enc_h0 <= 256 && n.enc_h0 % 32 == 0 &&
+        n.enc_h1 % 32 == 0 && n.enc_h1 + 4 <= (body ? FA_MIDP : FA_ENC_MIDP) && n.latent <= 32 && run_ok(1, n.enc_h0) &&
+        run_ok(1, n.enc_h1) && run_ok(1, (n.latent + 15) / 16 * 16)))
+    return false;
+  return !body || (n.ac_h0 % 32 == 0 && n.ac_h1 % 32 == 0 && 2 * n.ac_h0 <= 1024 && 2 * n.ac_h1 <= 512 &&
+                   2 * n.ac_h2 <= 256 && run_ok(1, 2 * n.ac_h0) && run_ok(2, n.ac_h1) && run_ok(2, n.ac_h2));
+}
+// LRL_ACT_ENC_FUSED=0: the prep kernel + three GEMM launches instead of the kernel's encoder part (read per call so a
+// test can switch it inside one process)
+static bool act_enc_fused(const lrl_ppo_net& n) {
+  const char* e = getenv("LRL_ACT_ENC_FUSED");
+  return !(e && e[0] == '0') && fused_envelope(n, false);
+}
+// LRL_ACT_FUSED=1 selects the one-launch act over the GEMM chain (A/B timing and the tests that compare the two; read
+// per call): off by default until it measures faster than the chain
+static bool fused_act_fits(const lrl_ppo_net& n) {
+  const char* e = getenv("LRL_ACT_FUSED");
+  return e && e[0] == '1' && fused_envelope(n, true);
+}
+// Launch act_fused_kernel, whole (`body`) or its encoder part: the float4 bits of the weight rows it reads, and the
+// instance specialised for the presets' widths where they and every bit hold.
+static void launch_act_fused(FusedActArgs& fa, bool body, hipStream_t st) {
+  const lrl_ppo_net& n = fa.net;
+  auto al = [&](int64_t off, int ld) { return (reinterpret_cast<uintptr_t>(fa.w + off) & 15) == 0 && ld % 4 == 0; };
+  fa.vec = (al(n.e2w, n.enc_h0) ? 2u : 0u) | (al(n.e3w, n.enc_h1) ? 4u : 0u);
+  if (body)
+    fa.vec |= (al(n.w1, n.num_obs + n.latent) ? 8u : 0u) | (al(n.w2, n.ac_h0) ? 16u : 0u) | (al(n.w3, n.ac_h1) ? 32u : 0u);
+  const bool preset = n.enc_h0 == 256 && n.enc_h1 == 128 && n.latent <= 32 &&
+                      (body ? n.ac_h0 == 512 && n.ac_h1 == 256 && n.ac_h2 == 128 && fa.vec == 62u : fa.vec == 6u);
+  const dim3 grid((fa.n + FA_R - 1) / FA_R), block(FA_THREADS);
+  const size_t lds = (body ? FA_LDS_FLOATS : FA_ENC_LDS_FLOATS) * sizeof(float);
+  if (body && preset) hipLaunchKernelGGL(act_fused_kernel<true>, grid, block, lds, st, fa);
+  else if (body) hipLaunchKernelGGL(act_fused_kernel<false>, grid, block, lds, st, fa);
+  else if (preset) hipLaunchKernelGGL((act_fused_kernel<true, true>), grid, block, lds, st, fa);
+  else hipLaunchKernelGGL((act_fused_kernel<false, true>), grid, block, lds, st, fa);
 }
 
 extern "C" int64_t lrl_ppo_act_workspace_bytes(const lrl_ppo_net* net, int32_t n) {
@@ -1527,36 +1667,18 @@ extern "C" int32_t lrl_ppo_act(const lrl_ppo_net* net, const float* params, cons
     return lrl_set_error(LRL_E_INVALID, "lrl_ppo_act: incomplete rollout store");
   const lrl_ppo_net& nt = *net;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (nt.plain) {
-    // plain tanh bodies over the observations alone (priv / hist may be NULL: they are only copied into the storage
-    // row when given): X = [obs | 0], three grouped [actor; critic] layers, the head.  The one-launch fused act is
-    // built around the presets' encoder and widths and is not taken here.
-    ActPlan P = make_act_plan(nt, n, static_cast<char*>(workspace));
-    G g{st, nullptr};
-    g.tanh_act = true;
-    const float* w = params;
-    const int no = nt.num_obs, XS = xs_of(nt);
-    hipLaunchKernelGGL(ppo_prep_kernel, dim3(prep_blocks(n, XS)), dim3(256), 0, st, obs, (const int64_t*)nullptr, n, no,
-                       XS, P.xa);
-    // (k runs over X's zero padding: see lrl_ppo_forward_backward)
-    g.nt(P.xa, XS, nullptr, w + nt.w1, no, P.h1, 2 * nt.ac_h0, w + nt.b1, n, 2 * nt.ac_h0, XS, true);
-    g.nt(P.h1, 2 * nt.ac_h0, nullptr, w + nt.w2, nt.ac_h0, P.h2, 2 * nt.ac_h1, w + nt.b2, n, nt.ac_h1, nt.ac_h0, true, 2,
-         nt.ac_h0, (int64_t)nt.ac_h1 * nt.ac_h0, nt.ac_h1, nt.ac_h1);
-    g.nt(P.h2, 2 * nt.ac_h1, nullptr, w + nt.w3, nt.ac_h1, P.h3, 2 * nt.ac_h2, w + nt.b3, n, nt.ac_h2, nt.ac_h1, true, 2,
-         nt.ac_h1, (int64_t)nt.ac_h2 * nt.ac_h1, nt.ac_h2, nt.ac_h2);
-    if (g.rc) return lrl_set_error(g.rc, "lrl_ppo_act: GEMM launch failed");
-    ActHeadArgs ah{};
-    ah.h3 = P.h3; ah.w4a = w + nt.w4a; ah.b4a = w + nt.b4a; ah.w4c = w + nt.w4c; ah.b4c = w + nt.b4c;
-    ah.stdv = w + nt.std_off; ah.obs = obs; ah.priv = priv; ah.hist = hist; ah.eps = eps;
-    ah.n = n; ah.na = nt.num_actions; ah.no = no; ah.np = nt.num_priv; ah.seed = seed; ah.counter = counter;
-    ah.row_offset = row_offset;
-    ah.actions = actions; ah.mu = mu; ah.values = values; ah.logp = logp;
-    if (store) ah.store = *store;
-    ah.store_row = store_row; ah.do_store = store ? 1 : 0;
-    hipLaunchKernelGGL(act_head_kernel, dim3((n + ACT_ROWS - 1) / ACT_ROWS), dim3(HEAD_THREADS), 0, st, ah);
-    return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_ppo_act: launch failed");
-  }
-  if (fused_act_fits(nt)) {  // one launch: act_fused_kernel
+  // the call's inputs and outputs, as the head kernel and the fused kernel both take them
+  auto io = [&](auto& a) {
+    a.obs = obs; a.priv = priv; a.hist = hist; a.eps = eps; a.n = n;
+    a.seed = seed; a.counter = counter; a.row_offset = row_offset;
+    a.actions = actions; a.mu = mu; a.values = values; a.logp = logp;
+    if (store) a.store = *store;
+    a.store_row = store_row; a.do_store = store ? 1 : 0;
+  };
+  // (a plain net — priv / hist may be NULL: they are only copied into the storage row when given — is the same chain
+  // with no encoder, no planes and tanh; the fused kernel is built around the presets' encoder and is not taken)
+  const bool full = !nt.plain;
+  if (full && fused_act_fits(nt)) {  // one launch: act_fused_kernel
     static const bool ok = [] {
       auto set = [](const void* f) {
         return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, FA_LDS_FLOATS * sizeof(float)) ==
@@ -1567,102 +1689,40 @@ extern "C" int32_t lrl_ppo_act(const lrl_ppo_net* net, const float* params, cons
     }();
     if (!ok) return lrl_set_error(LRL_E_HIP, "lrl_ppo_act: fused kernel LDS attribute");
     FusedActArgs fa{};
-    fa.w = params; fa.net = nt; fa.obs = obs; fa.priv = priv; fa.hist = hist; fa.eps = eps;
-    fa.n = n; fa.xs = xs_of(nt);
-    auto al = [&](int64_t off, int ld) { return ((reinterpret_cast<uintptr_t>(params + off) & 15) == 0 && ld % 4 == 0); };
-    const int nx = nt.num_obs + nt.latent;
-    fa.vec = (al(nt.e2w, nt.enc_h0) ? 2u : 0u) | (al(nt.e3w, nt.enc_h1) ? 4u : 0u) | (al(nt.w1, nx) ? 8u : 0u) |
-             (al(nt.w2, nt.ac_h0) ? 16u : 0u) | (al(nt.w3, nt.ac_h1) ? 32u : 0u);
-    fa.seed = seed; fa.counter = counter; fa.row_offset = row_offset;
-    fa.actions = actions; fa.mu = mu; fa.values = values; fa.logp = logp;
-    if (store) fa.store = *store;
-    fa.store_row = store_row; fa.do_store = store ? 1 : 0;
-    const bool preset = nt.enc_h0 == 256 && nt.enc_h1 == 128 && nt.latent <= 32 && nt.ac_h0 == 512 && nt.ac_h1 == 256 &&
-                        nt.ac_h2 == 128 && fa.vec == 62u;
-    if (preset)
-      hipLaunchKernelGGL(act_fused_kernel<true>, dim3((n + FA_R - 1) / FA_R), dim3(FA_THREADS),
-                         FA_LDS_FLOATS * sizeof(float), st, fa);
-    else
-      hipLaunchKernelGGL(act_fused_kernel<false>, dim3((n + FA_R - 1) / FA_R), dim3(FA_THREADS),
-                         FA_LDS_FLOATS * sizeof(float), st, fa);
+    fa.w = params; fa.net = nt; fa.xs = xs_of(nt);
+    io(fa);
+    launch_act_fused(fa, true, st);
     return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_ppo_act: launch failed");
   }
-  ActPlan P = make_act_plan(nt, n, static_cast<char*>(workspace));
-  G g{st, nullptr};
-  const float* w = params;
-  const int nx = nt.num_obs + nt.latent, XS = xs_of(nt);
+  Plan P = make_act_plan(nt, n, static_cast<char*>(workspace));
+  G g{st, params, n};
+  g.tanh_act = nt.plain;
+  const Net L = layers_of(nt);
   PlaneJob pj[PL_MAIN];
-  main_plane_jobs(nt, w, P.wpl, pj);
-  if (act_planes_on()) {
-    if (int rc = x6_planes_launch(pj, PL_FWD, st)) return lrl_set_error(rc, "lrl_ppo_act: planes launch failed");
-  } else {
-    for (auto& q : pj) q.dst = nullptr;
+  if (full) {
+    main_plane_jobs(nt, params, P.wpl, pj);
+    if (int rc = split_planes(pj, PL_FWD, act_planes_on(), st)) return lrl_set_error(rc, "lrl_ppo_act: planes launch failed");
+    g.with(pj);
   }
-  if (act_enc_fused(nt)) {  // X = [obs | encoder(priv) | 0] in one launch (act_fused_kernel<., true>)
+  if (full && act_enc_fused(nt)) {  // X = [obs | encoder(priv) | 0] in one launch (act_fused_kernel<., true>)
     FusedActArgs fa{};
-    fa.w = params; fa.net = nt; fa.obs = obs; fa.priv = priv; fa.n = n; fa.xs = XS; fa.xa_out = P.xa;
-    auto al = [&](int64_t off, int ld) { return ((reinterpret_cast<uintptr_t>(params + off) & 15) == 0 && ld % 4 == 0); };
-    fa.vec = (al(nt.e2w, nt.enc_h0) ? 2u : 0u) | (al(nt.e3w, nt.enc_h1) ? 4u : 0u);
-    const bool preset = nt.enc_h0 == 256 && nt.enc_h1 == 128 && nt.latent <= 32 && fa.vec == 6u;
-    if (preset)
-      hipLaunchKernelGGL((act_fused_kernel<true, true>), dim3((n + FA_R - 1) / FA_R), dim3(FA_THREADS),
-                         FA_ENC_LDS_FLOATS * sizeof(float), st, fa);
-    else
-      hipLaunchKernelGGL((act_fused_kernel<false, true>), dim3((n + FA_R - 1) / FA_R), dim3(FA_THREADS),
-                         FA_ENC_LDS_FLOATS * sizeof(float), st, fa);
+    fa.w = params; fa.net = nt; fa.obs = obs; fa.priv = priv; fa.n = n; fa.xs = (int)P.xa.ld; fa.xa_out = P.xa.p;
+    launch_act_fused(fa, false, st);
   } else {
-    hipLaunchKernelGGL(ppo_prep_kernel, dim3(prep_blocks(n, XS)), dim3(256), 0, st, obs,
-                       (const int64_t*)nullptr, n, nt.num_obs, XS, P.xa);
-    g.nt(priv, nt.num_priv, nullptr, w + nt.e1w, nt.num_priv, P.he1, nt.enc_h0, w + nt.e1b, n, nt.enc_h0, nt.num_priv,
-         true);
-    g.with(pj[PL_E2]).nt(P.he1, nt.enc_h0, nullptr, w + nt.e2w, nt.enc_h0, P.he2, nt.enc_h1, w + nt.e2b, n, nt.enc_h1,
-                         nt.enc_h0, true);
-    g.nt(P.he2, nt.enc_h1, nullptr, w + nt.e3w, nt.enc_h1, P.xa + nt.num_obs, XS, w + nt.e3b, n, nt.latent, nt.enc_h1,
-         false);
+    prep_x(nt, obs, nullptr, n, P.xa, st);
+    if (full) encoder_forward(g, L.enc, In{priv, nt.num_priv}, nullptr, P, cols_from(P.xa, nt.num_obs));
   }
-  g.with(pj[PL_W1]).nt(P.xa, XS, nullptr, w + nt.w1, nx, P.h1, 2 * nt.ac_h0, w + nt.b1, n, 2 * nt.ac_h0, XS, true);
-  g.with(pj[PL_W2]).nt(P.h1, 2 * nt.ac_h0, nullptr, w + nt.w2, nt.ac_h0, P.h2, 2 * nt.ac_h1, w + nt.b2, n, nt.ac_h1,
-                       nt.ac_h0, true, 2, nt.ac_h0, (int64_t)nt.ac_h1 * nt.ac_h0, nt.ac_h1, nt.ac_h1);
-  g.with(pj[PL_W3]).nt(P.h2, 2 * nt.ac_h1, nullptr, w + nt.w3, nt.ac_h1, P.h3, 2 * nt.ac_h2, w + nt.b3, n, nt.ac_h2,
-                       nt.ac_h1, true, 2, nt.ac_h1, (int64_t)nt.ac_h2 * nt.ac_h1, nt.ac_h2, nt.ac_h2);
+  body_forward(g, L.body, P);
   if (g.rc) return lrl_set_error(g.rc, "lrl_ppo_act: GEMM launch failed");
   ActHeadArgs ah{};
-  ah.h3 = P.h3; ah.w4a = w + nt.w4a; ah.b4a = w + nt.b4a; ah.w4c = w + nt.w4c; ah.b4c = w + nt.b4c;
-  ah.stdv = w + nt.std_off; ah.obs = obs; ah.priv = priv; ah.hist = hist; ah.eps = eps;
-  ah.n = n; ah.na = nt.num_actions; ah.no = nt.num_obs; ah.np = nt.num_priv; ah.seed = seed; ah.counter = counter;
-  ah.row_offset = row_offset;
-  ah.actions = actions; ah.mu = mu; ah.values = values; ah.logp = logp;
-  if (store) ah.store = *store;
-  ah.store_row = store_row; ah.do_store = store ? 1 : 0;
+  ah.h3 = P.h3.p; ah.w4a = params + nt.w4a; ah.b4a = params + nt.b4a; ah.w4c = params + nt.w4c; ah.b4c = params + nt.b4c;
+  ah.stdv = params + nt.std_off; ah.na = nt.num_actions; ah.no = nt.num_obs; ah.np = nt.num_priv;
+  io(ah);
   hipLaunchKernelGGL(act_head_kernel, dim3((n + ACT_ROWS - 1) / ACT_ROWS), dim3(HEAD_THREADS), 0, st, ah);
   return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_ppo_act: launch failed");
 }
 
 // ---- student act (actor_critic.py:160-164): latent = adaptation_module(hist), mean = actor_body([obs, latent]) ----
-struct StudentPlan {
-  float *xa, *hd1, *hd2, *h1, *h2, *h3, *wd1p;
-  int64_t bytes;
-};
-static StudentPlan make_student_plan(const lrl_ppo_net& n, int rows, char* base) {
-  StudentPlan p;
-  int64_t off = 0;
-  auto take = [&](int64_t floats) {
-    float* r = base ? reinterpret_cast<float*>(base + off) : nullptr;
-    off += ((floats * 4 + 255) / 256) * 256;
-    return r;
-  };
-  const int64_t R = rows;
-  p.xa = take(R * xs_of(n));
-  p.hd1 = take(R * n.ad_h0);
-  p.hd2 = take(R * HD2S);
-  p.h1 = take(R * n.ac_h0);
-  p.h2 = take(R * n.ac_h1);
-  p.h3 = take(R * n.ac_h2);
-  p.wd1p = take((int64_t)n.ad_h0 * hist_pad(n.num_hist));
-  p.bytes = off;
-  return p;
-}
-
 extern "C" int64_t lrl_ppo_act_student_workspace_bytes(const lrl_ppo_net* net, int32_t n) {
   if (check_net(net) || net->plain || n <= 0) return -1;
   return make_student_plan(*net, n, nullptr).bytes;
@@ -1676,34 +1736,22 @@ extern "C" int32_t lrl_ppo_act_student(const lrl_ppo_net* net, const float* para
   if (!params || !obs || !hist || !mean || !workspace || n <= 0)
     return lrl_set_error(LRL_E_INVALID, "lrl_ppo_act_student: null argument or n <= 0");
   const lrl_ppo_net& nt = *net;
-  const int hld = hist_ld ? hist_ld : nt.num_hist, hpad = hist_pad(nt.num_hist);
+  const int hld = hist_ld ? hist_ld : nt.num_hist;
   if (hld < nt.num_hist) return lrl_set_error(LRL_E_INVALID, "lrl_ppo_act_student: hist_ld < num_hist");
-  StudentPlan P = make_student_plan(nt, n, static_cast<char*>(workspace));
+  Plan P = make_student_plan(nt, n, static_cast<char*>(workspace));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  G g{st, nullptr};
-  const float* w = params;
-  const int nx = nt.num_obs + nt.latent, XS = xs_of(nt);
-  hipLaunchKernelGGL(ppo_prep_kernel, dim3(prep_blocks(n, XS)), dim3(256), 0, st, obs,
-                     (const int64_t*)nullptr, n, nt.num_obs, XS, P.xa);
-  if (hld >= hpad && hld % 4 == 0 && ((uintptr_t)hist & 15) == 0 && hpad != nt.num_hist) {
-    const int64_t cnt = (int64_t)nt.ad_h0 * hpad;
-    hipLaunchKernelGGL(pad_cols_kernel, dim3((unsigned)std::min<int64_t>((cnt + 255) / 256, 1024)), dim3(256), 0, st,
-                       w + nt.d1w, nt.ad_h0, nt.num_hist, hpad, P.wd1p);
-    g.nt(hist, hld, nullptr, P.wd1p, hpad, P.hd1, nt.ad_h0, w + nt.d1b, n, nt.ad_h0, hpad, true);
-  } else {
-    g.nt(hist, hld, nullptr, w + nt.d1w, nt.num_hist, P.hd1, nt.ad_h0, w + nt.d1b, n, nt.ad_h0, nt.num_hist, true);
-  }
-  g.nt(P.hd1, nt.ad_h0, nullptr, w + nt.d2w, nt.ad_h0, P.hd2, HD2S, w + nt.d2b, n, nt.ad_h1, nt.ad_h0, true);
-  g.nt(P.hd2, HD2S, nullptr, w + nt.d3w, nt.ad_h1, P.xa + nt.num_obs, XS, w + nt.d3b, n, nt.latent, nt.ad_h1, false);
-  // actor half of the grouped actor/critic layers (rows [0, h) of each grouped weight / bias)
-  g.nt(P.xa, XS, nullptr, w + nt.w1, nx, P.h1, nt.ac_h0, w + nt.b1, n, nt.ac_h0, XS, true);  // k-padding: see phase 1
-  g.nt(P.h1, nt.ac_h0, nullptr, w + nt.w2, nt.ac_h0, P.h2, nt.ac_h1, w + nt.b2, n, nt.ac_h1, nt.ac_h0, true);
-  g.nt(P.h2, nt.ac_h1, nullptr, w + nt.w3, nt.ac_h1, P.h3, nt.ac_h2, w + nt.b3, n, nt.ac_h2, nt.ac_h1, true);
-  g.nt(P.h3, nt.ac_h2, nullptr, w + nt.w4a, nt.ac_h2, mean, nt.num_actions, w + nt.b4a, n, nt.num_actions, nt.ac_h2,
-       false);
+  G g{st, params, n};
+  const Net L = layers_of(nt, true);  // the actor's half of the grouped layers: rows [0, h) of each weight / bias
+  const Buf lat = cols_from(P.xa, nt.num_obs);
+  prep_x(nt, obs, nullptr, n, P.xa, st);
+  adaptation_l1_forward(g, L.ad[0], In{hist, hld}, nullptr, P);
+  g.forward(L.ad[1], P.hd1, nullptr, P.hd2, true);
+  g.forward(L.ad[2], P.hd2, nullptr, lat, false);
+  body_forward(g, L.body, P);
+  g.forward(L.mean, P.h3, nullptr, Buf{mean, nt.num_actions}, false);
   if (g.rc) return lrl_set_error(g.rc, "lrl_ppo_act_student: GEMM launch failed");
   if (latent &&
-      hipMemcpy2DAsync(latent, (size_t)nt.latent * 4, P.xa + nt.num_obs, (size_t)XS * 4, (size_t)nt.latent * 4, n,
+      hipMemcpy2DAsync(latent, (size_t)nt.latent * 4, lat.p, (size_t)lat.ld * 4, (size_t)nt.latent * 4, n,
                        hipMemcpyDeviceToDevice, st) != hipSuccess)
     return lrl_set_error(LRL_E_HIP, "lrl_ppo_act_student: latent copy failed");
   return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_ppo_act_student: launch failed");
@@ -1722,177 +1770,91 @@ extern "C" int32_t lrl_ppo_forward_backward(const lrl_ppo_net* net, const float*
     return lrl_set_error(LRL_E_INVALID, "lrl_ppo_forward_backward: null argument");
   const lrl_ppo_net& n = *net;
   const int B = bt->batch;
+  const bool full = !n.plain;  // a plain net (the navigation policy): no encoder, no planes (fp32 B operands), tanh
   Plan P = make_plan(n, B, static_cast<char*>(workspace));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  G g{st, P.part + P.part_floats};
-  const float* w = params;
-  const int nx = n.num_obs + n.latent, XS = xs_of(n);
-  if (n.plain) {
-    // plain tanh bodies (the navigation policy): obs rows gathered at pitch XS = round16(num_obs), three grouped
-    // [actor; critic] layers, the head, the backward-data chain, three weight gradients — one stream, fp32 B operands
-    g.tanh_act = true;
-    const int h0 = n.ac_h0, h1 = n.ac_h1, h2 = n.ac_h2, na = n.num_actions;
-    hipLaunchKernelGGL(ppo_prep_kernel, dim3(prep_blocks(B, XS)), dim3(256), 0, st, bt->obs, bt->rows, B, n.num_obs, XS,
-                       P.xa);
-    // (k runs over X's zero columns nx..XS-1 against the next row's first weights / the biases after the last row)
-    g.nt(P.xa, XS, nullptr, w + n.w1, nx, P.h1, 2 * h0, w + n.b1, B, 2 * h0, XS, true);
-    g.nt(P.h1, 2 * h0, nullptr, w + n.w2, h0, P.h2, 2 * h1, w + n.b2, B, h1, h0, true, 2, h0, (int64_t)h1 * h0, h1, h1);
-    g.nt(P.h2, 2 * h1, nullptr, w + n.w3, h1, P.h3, 2 * h2, w + n.b3, B, h2, h1, true, 2, h1, (int64_t)h2 * h1, h2, h2);
-    if (g.rc) return lrl_set_error(g.rc, "lrl_ppo_forward_backward: forward GEMM launch failed");
-    SegList L{};
-    float* part = P.part;
-    const int hb = (B + HEAD_ROWS - 1) / HEAD_ROWS;
-    HeadArgs ha{};
-    ha.h3 = P.h3; ha.dh3 = P.dh3;
-    ha.w4a = w + n.w4a; ha.b4a = w + n.b4a; ha.w4c = w + n.w4c; ha.b4c = w + n.b4c; ha.stdv = w + n.std_off;
-    ha.actions = bt->actions; ha.old_mu = bt->mu; ha.old_sigma = bt->sigma; ha.tv = bt->values; ha.ret = bt->returns;
-    ha.adv = bt->adv; ha.old_logp = bt->logp; ha.rows = bt->rows;
-    ha.B = B; ha.na = na; ha.clip = hp->clip_param; ha.ent_coef = hp->entropy_coef; ha.vcoef = hp->value_loss_coef;
-    ha.clipped_value = hp->use_clipped_value_loss;
-    ha.part = part; ha.part_len = hp_len(na);
-    if (na == 3) hipLaunchKernelGGL((ppo_head_kernel<3, true>), dim3(hb), dim3(HEAD_THREADS), 0, st, ha);
-    else hipLaunchKernelGGL((ppo_head_kernel<HEAD_NA, true>), dim3(hb), dim3(HEAD_THREADS), 0, st, ha);
-    {
-      const int64_t pl = hp_len(na);
-      const float invB = 1.f / (float)B;
-      L.s[L.n++] = Seg{part + hp_w4a(na), grads + n.w4a, (int64_t)na * HEAD_W, pl, hb, 1.f};
-      L.s[L.n++] = Seg{part + hp_b4a(na), grads + n.b4a, na, pl, hb, 1.f};
-      L.s[L.n++] = Seg{part + hp_w4c(na), grads + n.w4c, HEAD_W, pl, hb, 1.f};
-      L.s[L.n++] = Seg{part + hp_b4c(na), grads + n.b4c, 1, pl, hb, 1.f};
-      L.s[L.n++] = Seg{part + hp_std(na), grads + n.std_off, na, pl, hb, 1.f};
-      L.s[L.n++] = Seg{part + hp_kl(na), grads + n.kl_slot, 1, pl, hb, invB};
-      L.s[L.n++] = Seg{part + hp_kl(na) + 1, &ctrl->mb[1], 1, pl, hb, invB};
-      L.s[L.n++] = Seg{part + hp_kl(na) + 2, &ctrl->mb[0], 1, pl, hb, invB};
-      part += ((hb * pl + 63) / 64) * 64;
-    }
-    g.nn(P.dh3, 2 * h2, w + n.w3, h1, P.dh2, 2 * h1, P.h2, 2 * h1, B, h1, h2, 2, h2, (int64_t)h2 * h1, h1, h1);
-    g.nn(P.dh2, 2 * h1, w + n.w2, h0, P.dh1, 2 * h0, P.h1, 2 * h0, B, h0, h1, 2, h1, (int64_t)h1 * h0, h0, h0);
-    g.tn(P.dh3, 2 * h2, P.h2, 2 * h1, nullptr, h2, h1, B, 2, h2, h1, part, grads + n.w3, grads + n.b3, L);
-    g.tn(P.dh2, 2 * h1, P.h1, 2 * h0, nullptr, h1, h0, B, 2, h1, h0, part, grads + n.w2, grads + n.b2, L);
-    g.tn(P.dh1, 2 * h0, P.xa, XS, nullptr, 2 * h0, nx, B, 1, 0, 0, part, grads + n.w1, grads + n.b1, L);
-    if (g.rc) return lrl_set_error(g.rc, "lrl_ppo_forward_backward: backward GEMM launch failed");
-    launch_seg(L, st);
-    return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_ppo_forward_backward: launch failed");
-  }
+  G g{st, params, B, P.part, P.part + P.part_floats};
+  g.tanh_act = n.plain;
+  const Net net_l = layers_of(n);
+  const Layer(&enc)[3] = net_l.enc;
+  const Layer(&body)[3] = net_l.body;
   // ---- forward ----
   PlaneJob pj[PL_MAIN];
-  main_plane_jobs(n, w, P.wpl, pj);
-  if (gemm_x6p_enabled()) {
-    if (int rc = x6_planes_launch(pj, PL_MAIN, st)) return lrl_set_error(rc, "lrl_ppo_forward_backward: planes launch failed");
-  } else {
-    for (auto& q : pj) q.dst = nullptr;
+  if (full) {
+    main_plane_jobs(n, params, P.wpl, pj);
+    if (int rc = split_planes(pj, PL_MAIN, gemm_x6p_enabled(), st))
+      return lrl_set_error(rc, "lrl_ppo_forward_backward: planes launch failed");
+    g.with(pj);
   }
-  auto PJ = [&](int i) -> const PlaneJob& { return pj[i]; };
-  hipLaunchKernelGGL(ppo_prep_kernel, dim3(prep_blocks(B, XS)), dim3(256), 0, st, bt->obs,
-                     bt->rows, B, n.num_obs, XS, P.xa);
-  g.nt(bt->priv, n.num_priv, bt->rows, w + n.e1w, n.num_priv, P.he1, n.enc_h0, w + n.e1b, B, n.enc_h0, n.num_priv, true);
-  g.with(PJ(PL_E2)).nt(P.he1, n.enc_h0, nullptr, w + n.e2w, n.enc_h0, P.he2, n.enc_h1, w + n.e2b, B, n.enc_h1, n.enc_h0, true);
-  g.nt(P.he2, n.enc_h1, nullptr, w + n.e3w, n.enc_h1, P.xa + n.num_obs, XS, w + n.e3b, B, n.latent, n.enc_h1, false);
-  // k runs over all XS columns of X: columns nx..XS-1 are zero, so the extra products (with the next
-  // row's first weights, or the first biases after the last row — finite values; zero planes on the x6p path) add
-  // exactly 0, and the product takes the unguarded float4 path
-  g.with(PJ(PL_W1)).nt(P.xa, XS, nullptr, w + n.w1, nx, P.h1, 2 * n.ac_h0, w + n.b1, B, 2 * n.ac_h0, XS, true);
-  g.with(PJ(PL_W2)).nt(P.h1, 2 * n.ac_h0, nullptr, w + n.w2, n.ac_h0, P.h2, 2 * n.ac_h1, w + n.b2, B, n.ac_h1, n.ac_h0,
-                       true, 2, n.ac_h0, (int64_t)n.ac_h1 * n.ac_h0, n.ac_h1, n.ac_h1);
-  g.with(PJ(PL_W3)).nt(P.h2, 2 * n.ac_h1, nullptr, w + n.w3, n.ac_h1, P.h3, 2 * n.ac_h2, w + n.b3, B, n.ac_h2, n.ac_h1,
-                       true, 2, n.ac_h1, (int64_t)n.ac_h2 * n.ac_h1, n.ac_h2, n.ac_h2);
+  const In priv{bt->priv, n.num_priv};
+  prep_x(n, bt->obs, bt->rows, B, P.xa, st);
+  if (full) encoder_forward(g, enc, priv, bt->rows, P, cols_from(P.xa, n.num_obs));
+  body_forward(g, body, P);
   if (g.rc) return lrl_set_error(g.rc, "lrl_ppo_forward_backward: forward GEMM launch failed");
   // ---- head ----
   SegList L{};
-  float* part = P.part;
-  const int hb = (B + HEAD_ROWS - 1) / HEAD_ROWS;
-  const int na = n.num_actions;
-  HeadArgs ha{};
-  ha.h3 = P.h3; ha.dh3 = P.dh3;
-  ha.w4a = w + n.w4a; ha.b4a = w + n.b4a; ha.w4c = w + n.w4c; ha.b4c = w + n.b4c; ha.stdv = w + n.std_off;
-  ha.actions = bt->actions; ha.old_mu = bt->mu; ha.old_sigma = bt->sigma; ha.tv = bt->values; ha.ret = bt->returns;
-  ha.adv = bt->adv; ha.old_logp = bt->logp; ha.rows = bt->rows;
-  ha.B = B; ha.na = na; ha.clip = hp->clip_param; ha.ent_coef = hp->entropy_coef; ha.vcoef = hp->value_loss_coef;
-  ha.clipped_value = hp->use_clipped_value_loss;
-  ha.part = part; ha.part_len = hp_len(na);
-  hipLaunchKernelGGL((ppo_head_kernel<HEAD_NA, false>), dim3(hb), dim3(HEAD_THREADS), 0, st, ha);
-  {
-    const int64_t pl = hp_len(na);
-    const float invB = 1.f / (float)B;
-    L.s[L.n++] = Seg{part + hp_w4a(na), grads + n.w4a, (int64_t)na * HEAD_W, pl, hb, 1.f};
-    L.s[L.n++] = Seg{part + hp_b4a(na), grads + n.b4a, na, pl, hb, 1.f};
-    L.s[L.n++] = Seg{part + hp_w4c(na), grads + n.w4c, HEAD_W, pl, hb, 1.f};
-    L.s[L.n++] = Seg{part + hp_b4c(na), grads + n.b4c, 1, pl, hb, 1.f};
-    L.s[L.n++] = Seg{part + hp_std(na), grads + n.std_off, na, pl, hb, 1.f};
-    L.s[L.n++] = Seg{part + hp_kl(na), grads + n.kl_slot, 1, pl, hb, invB};
-    L.s[L.n++] = Seg{part + hp_kl(na) + 1, &ctrl->mb[1], 1, pl, hb, invB};
-    L.s[L.n++] = Seg{part + hp_kl(na) + 2, &ctrl->mb[0], 1, pl, hb, invB};
-    part += ((hb * pl + 63) / 64) * 64;
-  }
+  launch_loss_head(n, params, grads, bt, hp, ctrl, P, g.part, L, st);
   // ---- backward ----
-  // the data-gradient chain first (dH2, dH1, the latent gradient), then the encoder's chain and the actor / critic
-  // weight gradients: packed into three multi-problem launches (bwd_multi_mode), or, as the fallback, the chain forked to
-  // the library's second stream while the weight gradients run here; the split-k reduction waits for all of them
-  const int h0 = n.ac_h0, h1 = n.ac_h1, h2 = n.ac_h2;
-  g.with(PJ(PL_W3T)).nn(P.dh3, 2 * h2, w + n.w3, h1, P.dh2, 2 * h1, P.h2, 2 * h1, B, h1, h2, 2, h2, (int64_t)h2 * h1, h1, h1);
-  g.with(PJ(PL_W2T)).nn(P.dh2, 2 * h1, w + n.w2, h0, P.dh1, 2 * h0, P.h1, 2 * h0, B, h0, h1, 2, h1, (int64_t)h1 * h0, h0, h0);
-  // d latent = dH1 [W1a; W1c][:, num_obs:]  (sum over actor and critic halves: one reduction of length 2*h0)
-  g.nn(P.dh1, 2 * h0, w + n.w1 + n.num_obs, nx, P.dlat, LATS, nullptr, 0, B, n.latent, 2 * h0);
-  if (const int mode = bwd_multi_mode()) {
-    // the eight products are collected in the fallback path's order (so the partial area and the segment list are
-    // laid out exactly as there), then launched as three sets: the encoder's chain needs dlat -> dhe2 -> dhe1 in turn,
-    // the actor / critic weight gradients need none of them
-    enum { DWE3, DHE2, DWE2, DHE1, DWE1, DW3, DW2, DW1, NJOBS };
-    GemmJob jobs[NJOBS];
-    G gc{st, g.part_end};
-    gc.jobs = jobs;
-    gc.max_jobs = NJOBS;
-    gc.tn(P.dlat, LATS, P.he2, n.enc_h1, nullptr, n.latent, n.enc_h1, B, 1, 0, 0, part, grads + n.e3w, grads + n.e3b, L);
-    gc.nn(P.dlat, LATS, w + n.e3w, n.enc_h1, P.dhe2, n.enc_h1, P.he2, n.enc_h1, B, n.enc_h1, n.latent);
-    gc.tn(P.dhe2, n.enc_h1, P.he1, n.enc_h0, nullptr, n.enc_h1, n.enc_h0, B, 1, 0, 0, part, grads + n.e2w, grads + n.e2b, L);
-    gc.with(PJ(PL_E2T)).nn(P.dhe2, n.enc_h1, w + n.e2w, n.enc_h0, P.dhe1, n.enc_h0, P.he1, n.enc_h0, B, n.enc_h0, n.enc_h1);
-    gc.tn(P.dhe1, n.enc_h0, bt->priv, n.num_priv, bt->rows, n.enc_h0, n.num_priv, B, 1, 0, 0, part, grads + n.e1w,
-          grads + n.e1b, L);
-    gc.tn(P.dh3, 2 * h2, P.h2, 2 * h1, nullptr, h2, h1, B, 2, h2, h1, part, grads + n.w3, grads + n.b3, L);
-    gc.tn(P.dh2, 2 * h1, P.h1, 2 * h0, nullptr, h1, h0, B, 2, h1, h0, part, grads + n.w2, grads + n.b2, L);
-    gc.tn(P.dh1, 2 * h0, P.xa, XS, nullptr, 2 * h0, nx, B, 1, 0, 0, part, grads + n.w1, grads + n.b1, L);
-    int rc = gc.rc ? gc.rc : (gc.njobs == NJOBS ? 0 : LRL_E_INVALID);
-    static const int hosts[3][3] = {{DW3, DW1, DW2}, {DW3, DW2, DW1}, {DW2, DW1, DW3}};
-    const int* host = g_timer.on ? hosts[0] : hosts[mode - 1];
-    if (!rc) rc = launch_jobs(jobs, {DWE3, DHE2, host[0]}, st);
-    if (!rc && g_timer.on) {
-      // the timed product (dW2: bench.py --full's roofline_update_gemm) alone, so its time keeps its meaning: dW1
-      // hosts dW2's rider, and the other two riders go in a launch of their own
-      rc = launch_jobs(jobs, {DWE2, DHE1}, st);
-      timer_begin(st);
-      if (!rc) rc = launch_jobs(jobs, {DW2}, st);
-      timer_end(st);
-      if (!rc) rc = launch_jobs(jobs, {DWE1, DW1}, st);
-    } else if (!rc) {
-      rc = launch_jobs(jobs, {DWE2, DHE1, host[1]}, st);
-      if (!rc) rc = launch_jobs(jobs, {DWE1, host[2]}, st);
-    }
-    if (rc) return lrl_set_error(rc, "lrl_ppo_forward_backward: backward GEMM launch failed");
-    launch_seg(L, st);
-    return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_ppo_forward_backward: launch failed");
+  // the data-gradient chain first (dH2, dH1, the latent gradient), then the tail: the encoder's chain (it needs dlat ->
+  // dhe2 -> dhe1 in turn) and the actor / critic weight gradients (they need none of them), collected in this one order,
+  // which is the order of their partials and segments, and launched as the mode says; the split-k reduction waits
+  // for all of them
+  g.backward_data(body[2], P.dh3, P.dh2, P.h2);
+  g.backward_data(body[1], P.dh2, P.dh1, P.h1);
+  if (full) g.backward_data(net_l.dlat, P.dh1, P.dlat, In{});
+  enum { DWE3, DHE2, DWE2, DHE1, DWE1, DW3, DW2, DW1, NJOBS };
+  GemmJob jobs[NJOBS];
+  const int first = full ? 0 : DW3;
+  g.collect(jobs, first, NJOBS);
+  if (full) {
+    g.weight_grad(enc[2], P.dlat, P.he2, nullptr, grads, L);
+    g.backward_data(enc[2], P.dlat, P.dhe2, P.he2);
+    g.weight_grad(enc[1], P.dhe2, P.he1, nullptr, grads, L);
+    g.backward_data(enc[1], P.dhe2, P.dhe1, P.he1);
+    g.weight_grad(enc[0], P.dhe1, priv, bt->rows, grads, L);
   }
-  Fork* fk = fork_for_device(st);
-  G ge{fk ? fk->st : st, g.part_end};
-  if (fk) {
-    if (hipEventRecord(fk->go, st) != hipSuccess || hipStreamWaitEvent(fk->st, fk->go, 0) != hipSuccess)
+  g.weight_grad(body[2], P.dh3, P.h2, nullptr, grads, L);
+  g.weight_grad(body[1], P.dh2, P.h1, nullptr, grads, L);
+  g.weight_grad(body[0], P.dh1, P.xa, nullptr, grads, L);
+  int rc = g.rc ? g.rc : (g.njobs == NJOBS ? 0 : LRL_E_INVALID);
+  if (rc) return lrl_set_error(rc, "lrl_ppo_forward_backward: backward GEMM launch failed");
+  // the launches: one per product (mode 0, and a plain net's three), or the mode's three sets.  With the timing hook
+  // on, the timed product (dW2: bench.py --full's roofline_update_gemm) goes alone, so its time keeps its meaning:
+  // dW1 hosts dW2's rider, and the other two riders go in a launch of their own
+  struct Set { int n, i[MAX_MULTI_JOBS]; };
+  Set sets[NJOBS];
+  int ns = 0;
+  const int mode = full ? bwd_multi_mode() : 0;
+  if (mode == 0) {
+    for (int i = first; i < NJOBS; ++i) sets[ns++] = Set{1, {i}};
+  } else if (g_timer.on) {
+    sets[ns++] = Set{3, {DWE3, DHE2, DW3}};
+    sets[ns++] = Set{2, {DWE2, DHE1}};
+    sets[ns++] = Set{1, {DW2}};
+    sets[ns++] = Set{2, {DWE1, DW1}};
+  } else {
+    static const int hosts[3][3] = {{DW3, DW1, DW2}, {DW3, DW2, DW1}, {DW2, DW1, DW3}};
+    const int* host = hosts[mode - 1];
+    sets[ns++] = Set{3, {DWE3, DHE2, host[0]}};
+    sets[ns++] = Set{3, {DWE2, DHE1, host[1]}};
+    sets[ns++] = Set{2, {DWE1, host[2]}};
+  }
+  // (mode 0: the encoder's five on the fork stream, where there is one)
+  Fork* fk = mode == 0 && full ? fork_for_device(st) : nullptr;
+  if (fk && (hipEventRecord(fk->go, st) != hipSuccess || hipStreamWaitEvent(fk->st, fk->go, 0) != hipSuccess))
+    return lrl_set_error(LRL_E_HIP, "lrl_ppo_forward_backward: stream fork failed");
+  for (int s = 0; s < ns && !rc; ++s) {
+    const int lead = sets[s].i[0];
+    const bool timed = full && sets[s].n == 1 && lead == DW2;
+    if (timed) timer_begin(st);
+    rc = launch_jobs(jobs, sets[s].i, sets[s].n, fk && lead < DW3 ? fk->st : st);
+    if (timed) timer_end(st);
+    if (fk && lead == DWE1 && hipEventRecord(fk->done, fk->st) != hipSuccess)
       return lrl_set_error(LRL_E_HIP, "lrl_ppo_forward_backward: stream fork failed");
   }
-  ge.tn(P.dlat, LATS, P.he2, n.enc_h1, nullptr, n.latent, n.enc_h1, B, 1, 0, 0, part, grads + n.e3w, grads + n.e3b, L);
-  ge.nn(P.dlat, LATS, w + n.e3w, n.enc_h1, P.dhe2, n.enc_h1, P.he2, n.enc_h1, B, n.enc_h1, n.latent);
-  ge.tn(P.dhe2, n.enc_h1, P.he1, n.enc_h0, nullptr, n.enc_h1, n.enc_h0, B, 1, 0, 0, part, grads + n.e2w, grads + n.e2b, L);
-  ge.with(PJ(PL_E2T)).nn(P.dhe2, n.enc_h1, w + n.e2w, n.enc_h0, P.dhe1, n.enc_h0, P.he1, n.enc_h0, B, n.enc_h0, n.enc_h1);
-  ge.tn(P.dhe1, n.enc_h0, bt->priv, n.num_priv, bt->rows, n.enc_h0, n.num_priv, B, 1, 0, 0, part, grads + n.e1w,
-        grads + n.e1b, L);
-  if (fk && hipEventRecord(fk->done, fk->st) != hipSuccess)
-    return lrl_set_error(LRL_E_HIP, "lrl_ppo_forward_backward: stream fork failed");
-  g.tn(P.dh3, 2 * h2, P.h2, 2 * h1, nullptr, h2, h1, B, 2, h2, h1, part, grads + n.w3, grads + n.b3, L);
-  timer_begin(st);
-  g.tn(P.dh2, 2 * h1, P.h1, 2 * h0, nullptr, h1, h0, B, 2, h1, h0, part, grads + n.w2, grads + n.b2, L);
-  timer_end(st);
-  g.tn(P.dh1, 2 * h0, P.xa, XS, nullptr, 2 * h0, nx, B, 1, 0, 0, part, grads + n.w1, grads + n.b1, L);
   if (fk && hipStreamWaitEvent(st, fk->done, 0) != hipSuccess)
     return lrl_set_error(LRL_E_HIP, "lrl_ppo_forward_backward: stream join failed");
-  if (g.rc || ge.rc) return lrl_set_error(g.rc ? g.rc : ge.rc, "lrl_ppo_forward_backward: backward GEMM launch failed");
+  if (rc) return lrl_set_error(rc, "lrl_ppo_forward_backward: backward GEMM launch failed");
   launch_seg(L, st);
   return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_ppo_forward_backward: launch failed");
 }
@@ -1933,42 +1895,35 @@ extern "C" int32_t lrl_ppo_adaptation_forward_backward(const lrl_ppo_net* net, c
     return lrl_set_error(LRL_E_INVALID, "lrl_ppo_adaptation_forward_backward: null argument");
   const lrl_ppo_net& n = *net;
   const int B = bt->batch;
+  const int hld = bt->hist_ld ? bt->hist_ld : n.num_hist;
+  if (hld < n.num_hist) return lrl_set_error(LRL_E_INVALID, "lrl_ppo_adaptation: hist_ld < num_hist");
   Plan P = make_plan(n, B, static_cast<char*>(workspace));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  G g{st, P.part + P.part_floats};
-  const float* w = params;
+  G g{st, params, B, P.part, P.part + P.part_floats};
+  const Net net_l = layers_of(n);
+  const Layer(&ad)[3] = net_l.ad;
   // target = env_factor_encoder(priv) with the just-updated weights (torch.no_grad, ppo.py:159-160), read from
   // enc_params (a snapshot of them taken right after the optimiser step, so the next step may proceed) or params
   const float* we = enc_params ? enc_params : params;
   PlaneJob pj[PL_ADAPT];
-  adapt_plane_jobs(n, w, we, P.wpl, pj);
-  if (gemm_x6p_enabled()) {
-    if (int rc = x6_planes_launch(pj, PL_ADAPT, st)) return lrl_set_error(rc, "lrl_ppo_adaptation: planes launch failed");
-  } else {
-    for (auto& q : pj) q.dst = nullptr;
-  }
-  g.nt(bt->priv, n.num_priv, bt->rows, we + n.e1w, n.num_priv, P.he1, n.enc_h0, we + n.e1b, B, n.enc_h0, n.num_priv, true);
-  g.with(pj[PL_AE2]).nt(P.he1, n.enc_h0, nullptr, we + n.e2w, n.enc_h0, P.he2, n.enc_h1, we + n.e2b, B, n.enc_h1, n.enc_h0, true);
-  g.nt(P.he2, n.enc_h1, nullptr, we + n.e3w, n.enc_h1, P.tgt, LATS, we + n.e3b, B, n.latent, n.enc_h1, false);
+  adapt_plane_jobs(n, params, we, P.wpl, pj);
+  if (int rc = split_planes(pj, PL_ADAPT, gemm_x6p_enabled(), st))
+    return lrl_set_error(rc, "lrl_ppo_adaptation: planes launch failed");
+  g.with(pj);
+  g.w = we;
+  encoder_forward(g, net_l.tgt, In{bt->priv, n.num_priv}, bt->rows, P, P.tgt);
+  g.w = params;
   // prediction = adaptation_module(obs_history)
-  const int hld = bt->hist_ld ? bt->hist_ld : n.num_hist, hpad = hist_pad(n.num_hist);
-  if (hld < n.num_hist) return lrl_set_error(LRL_E_INVALID, "lrl_ppo_adaptation: hist_ld < num_hist");
-  if (hld >= hpad && hld % 4 == 0 && ((uintptr_t)bt->hist & 15) == 0 && hpad != n.num_hist) {
-    // history rows carry finite padding up to hpad: run k = hpad against zero-padded weights (float4 rows)
-    const int64_t cnt = (int64_t)n.ad_h0 * hpad;
-    hipLaunchKernelGGL(pad_cols_kernel, dim3((unsigned)std::min<int64_t>((cnt + 255) / 256, 1024)), dim3(256), 0, st,
-                       w + n.d1w, n.ad_h0, n.num_hist, hpad, P.wd1p);
-    g.with(pj[PL_D1]).nt(bt->hist, hld, bt->rows, P.wd1p, hpad, P.hd1, n.ad_h0, w + n.d1b, B, n.ad_h0, hpad, true);
-  } else {
-    g.nt(bt->hist, hld, bt->rows, w + n.d1w, n.num_hist, P.hd1, n.ad_h0, w + n.d1b, B, n.ad_h0, n.num_hist, true);
-  }
-  g.nt(P.hd1, n.ad_h0, nullptr, w + n.d2w, n.ad_h0, P.hd2, HD2S, w + n.d2b, B, n.ad_h1, n.ad_h0, true);
+  const In hist{bt->hist, hld};
+  adaptation_l1_forward(g, ad[0], hist, bt->rows, P);
+  g.forward(ad[1], P.hd1, nullptr, P.hd2, true);
   if (g.rc) return lrl_set_error(g.rc, "lrl_ppo_adaptation: forward GEMM launch failed");
   SegList L{};
-  float* part = P.part;
+  float*& part = g.part;
   const int hb = (B + HEAD_ROWS - 1) / HEAD_ROWS;
   AdaptHeadArgs aa{};
-  aa.hd2 = P.hd2; aa.ldh = HD2S; aa.tgt = P.tgt; aa.ldt = LATS; aa.dhd2 = P.dhd2; aa.w = w + n.d3w; aa.b = w + n.d3b;
+  aa.hd2 = P.hd2.p; aa.ldh = HD2S; aa.tgt = P.tgt.p; aa.ldt = LATS; aa.dhd2 = P.dhd2.p; aa.w = params + n.d3w;
+  aa.b = params + n.d3b;
   aa.B = B; aa.H = n.ad_h1; aa.L = n.latent; aa.part = part; aa.part_len = n.latent * n.ad_h1 + n.latent + 1;
   if (aa.H == 32 && aa.L == 18)
     hipLaunchKernelGGL((adapt_head_kernel<32, 18>), dim3(hb), dim3(HEAD_THREADS), 0, st, aa);
@@ -1982,10 +1937,9 @@ extern "C" int32_t lrl_ppo_adaptation_forward_backward(const lrl_ppo_net* net, c
                      1.f / ((float)B * (float)n.latent)};
     part += ((hb * pl + 63) / 64) * 64;
   }
-  g.tn(P.dhd2, HD2S, P.hd1, n.ad_h0, nullptr, n.ad_h1, n.ad_h0, B, 1, 0, 0, part, grads + n.d2w, grads + n.d2b, L);
-  g.with(pj[PL_D2T]).nn(P.dhd2, HD2S, w + n.d2w, n.ad_h0, P.dhd1, n.ad_h0, P.hd1, n.ad_h0, B, n.ad_h0, n.ad_h1);
-  g.tn(P.dhd1, n.ad_h0, bt->hist, hld, bt->rows, n.ad_h0, n.num_hist, B, 1, 0, 0, part, grads + n.d1w,
-       grads + n.d1b, L);
+  g.weight_grad(ad[1], P.dhd2, P.hd1, nullptr, grads, L);
+  g.backward_data(ad[1], P.dhd2, P.dhd1, P.hd1);
+  g.weight_grad(ad[0], P.dhd1, hist, bt->rows, grads, L);
   if (g.rc) return lrl_set_error(g.rc, "lrl_ppo_adaptation: backward GEMM launch failed");
   launch_seg(L, st);
   return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_ppo_adaptation: launch failed");
@@ -2011,52 +1965,54 @@ extern "C" int32_t lrl_ppo_adaptation_step(const lrl_ppo_net* net, float* params
   return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_ppo_adaptation_step: launch failed");
 }
 
-// ---- GEMM test entry point ----
+// ---- GEMM test entry points: one product (lrl_gemm_f32), and the update's grouped / pitched operand forms, alone
+// (lrl_gemm_f32_ex) or as a multi-problem launch (lrl_gemm_f32_multi).  A TN product is the update's split-k job
+// (splitk_job) in the caller's workspace with its reduction into C (and db = bias); planes are plane_job's. ----
+// Split B into planes in the workspace, point p at them: for the x6p kernel (and nothing else) to run the product
+static int use_test_planes(GemmP& p, int layout, int groups, float* workspace, int64_t workspace_floats,
+                           hipStream_t st) {
+  PlaneJob j = plane_job(p.B, p.ldb, layout, p.N, p.K, groups, p.gb);
+  j.dst = reinterpret_cast<uint16_t*>(workspace);
+  if (!workspace || plane_elems(j) > 2 * workspace_floats)
+    return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32(_ex): workspace too small for the planes");
+  if (int rc = x6_planes_launch(&j, 1, st)) return lrl_set_error(rc, "lrl_gemm_f32(_ex): planes launch failed");
+  gemm_use_planes(p, j);
+  return 0;
+}
+
 extern "C" int32_t lrl_gemm_f32(int32_t layout, int32_t epi, int32_t M, int32_t N, int32_t K, const float* A,
                                 int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, const float* bias,
                                 const float* aux, int64_t ld_aux, const int64_t* rows, float* workspace,
                                 int64_t workspace_floats, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
-  GemmP p{};
-  p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc; p.bias = bias; p.aux = aux; p.ld_aux = ld_aux;
-  p.M = M; p.N = N; p.K = K; p.splits = 1;
   if ((epi == EPI_BIAS_TANH && (layout & 0xff) != GEMM_NT) || (epi == EPI_DTANH && (layout & 0xff) != GEMM_NN))
     return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32: epi 5 is an NT epilogue, epi 6 an NN one");
   if (epi == EPI_DTANH && !aux) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32: epi 6 needs aux");
   if (layout == GEMM_TN) {
     // split-k into the workspace, then reduce into C (C must be [M][N] contiguous: ldc == N)
     if (ldc != N) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32: TN needs ldc == N");
-    int splits = gemm_pick_splits(M, N, K, 1);
-    if (const char* e = getenv("LRL_GEMM_SPLITS")) {  // development knob (scripts/tn_sweep.py)
-      const int s = atoi(e);
-      if (s > 0) splits = s;
-    }
-    if ((int64_t)splits * ((int64_t)M * N + M) > workspace_floats)
+    int splits = 0;
+    if (const char* e = getenv("LRL_GEMM_SPLITS")) splits = std::max(atoi(e), 0);  // development knob (scripts/tn_sweep.py)
+    SplitK k;
+    float* part = workspace;
+    if (!splitk_job(M, N, K, 1, splits, In{A, lda}, 0, In{B, ldb}, 0, rows, C, const_cast<float*>(bias), part,
+                    workspace + workspace_floats, k))
       return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32: workspace too small");
-    p.b_rows = rows; p.splits = splits; p.kps = (K + splits - 1) / splits;
-    p.C = workspace; p.gc = (int64_t)M * N; p.part_stride = (int64_t)M * N;
-    p.bias_part = workspace + (int64_t)splits * M * N;
-    int rc = gemm_launch(p, GEMM_TN, EPI_PARTIAL, 1, st);
-    if (rc) return lrl_set_error(rc, "lrl_gemm_f32: launch failed");
+    if (int rc = gemm_launch(k.p, GEMM_TN, EPI_PARTIAL, 1, st)) return lrl_set_error(rc, "lrl_gemm_f32: launch failed");
     SegList L{};
-    L.s[L.n++] = Seg{workspace, C, (int64_t)M * N, (int64_t)M * N, splits, 1.f};
-    if (bias) L.s[L.n++] = Seg{p.bias_part, const_cast<float*>(bias), M, M, splits, 1.f};  // bias = db output
+    L.s[L.n++] = k.s[0];
+    if (bias) L.s[L.n++] = k.s[1];  // bias = db output
     launch_seg(L, st);
     return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_gemm_f32: launch failed");
   }
+  GemmP p{};
+  p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc; p.bias = bias; p.aux = aux; p.ld_aux = ld_aux;
+  p.M = M; p.N = N; p.K = K; p.splits = 1;
   p.a_rows = rows;
-  if (layout & 0x100) {
-    // pre-split B: planes of op(B) built in the workspace, then the x6p kernel (and nothing else) runs the product
+  if (layout & 0x100) {  // pre-split B
     layout &= 0xff;
     if (layout != GEMM_NT && layout != GEMM_NN) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32: planes need NT / NN");
-    PlaneJob j{};
-    j.W = B; j.ldw = ldb; j.gsrc = 0; j.groups = 1; j.trans = layout == GEMM_NN ? 1 : 0;
-    j.rows = layout == GEMM_NN ? K : N; j.cols = layout == GEMM_NN ? N : K;
-    j.dst = reinterpret_cast<uint16_t*>(workspace);
-    if (!workspace || plane_elems(j) > 2 * workspace_floats)
-      return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32: workspace too small for the planes");
-    if (int rc = x6_planes_launch(&j, 1, st)) return lrl_set_error(rc, "lrl_gemm_f32: planes launch failed");
-    gemm_use_planes(p, j);
+    if (int rc = use_test_planes(p, layout, 1, workspace, workspace_floats, st)) return rc;
     int rc = gemm_launch(p, layout, epi, 1, st);
     if (rc) return lrl_set_error(rc, "lrl_gemm_f32: launch failure");
     return (gemm_last_path() & 0xff) == FAM_X6P
@@ -2067,85 +2023,71 @@ extern "C" int32_t lrl_gemm_f32(int32_t layout, int32_t epi, int32_t M, int32_t 
   return rc ? lrl_set_error(rc, "lrl_gemm_f32: bad layout/epilogue or launch failure") : 0;
 }
 
-// ---- GEMM test entry point, the update's grouped / pitched operand forms ----
-// The product a descriptor names as gemm_launch takes it (planes apart), and the split count of a TN product.
-static int32_t desc_job(const lrl_gemm_desc* d, GemmJob& job, int& splits) {
+// The product a descriptor names as gemm_launch takes it (planes apart); for a TN product, its reduction in k.s.
+static int32_t desc_job(const lrl_gemm_desc* d, GemmJob& job, SplitK& k) {
   if (!d || !d->A || !d->B || !d->C || d->M <= 0 || d->N <= 0 || d->K <= 0 || d->groups <= 0 || d->splits < 0)
     return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: bad argument");
   const int layout = d->layout, epi = d->epi, groups = d->groups, M = d->M, N = d->N, K = d->K;
   if (d->path_out) *d->path_out = 0;
+  if (layout == GEMM_TN) {
+    if (epi != EPI_PARTIAL || d->planes) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: TN is epi 4, no planes");
+    if (d->ldc != N) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: TN needs ldc == N");
+    if (d->splits) {  // (only an override is judged: the update's own count stands as it is)
+      const int kps = ((K + d->splits - 1) / d->splits + 15) / 16 * 16;  // (gemm_launch rounds a split to whole 16-row slices)
+      if ((int64_t)(d->splits - 1) * kps >= K) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: a split would be empty");
+    }
+    float* part = d->workspace;
+    if (!d->workspace || !splitk_job(M, N, K, groups, d->splits, In{d->A, d->lda}, d->ga, In{d->B, d->ldb}, d->gb,
+                                     d->rows, d->C, d->bias, part, d->workspace + d->workspace_floats, k))
+      return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: workspace too small");
+    job =GemmJob{k.p, layout, epi, groups};
+    return 0;
+  }
+  if (layout != GEMM_NT && layout != GEMM_NN) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: layout is 0, 2 or 3");
+  if (d->splits > 1 || epi == EPI_PARTIAL) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: NT / NN are not split");
+  if ((epi == EPI_BIAS_TANH && layout != GEMM_NT) || (epi == EPI_DTANH && layout != GEMM_NN))
+    return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: epi 5 is an NT epilogue, epi 6 an NN one");
+  if ((epi == EPI_DELU || epi == EPI_DTANH) && !d->aux) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: epi 3 / 6 need aux");
+  if ((epi == EPI_BIAS || epi == EPI_BIAS_ELU || epi == EPI_BIAS_TANH) && !d->bias)
+    return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: epi 1 / 2 / 5 need bias");
   GemmP p{};
   p.A = d->A; p.lda = d->lda; p.B = d->B; p.ldb = d->ldb; p.aux = d->aux; p.ld_aux = d->ld_aux;
   p.M = M; p.N = N; p.K = K; p.splits = 1;
   p.ga = d->ga; p.gb = d->gb; p.gaux = d->gaux;
-  splits = 1;
-  if (layout == GEMM_TN) {
-    // G::tn's layout: [split][group][M][N] partials, [split][group][M] bias partials behind them, one reduction
-    if (epi != EPI_PARTIAL || d->planes) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: TN is epi 4, no planes");
-    if (d->ldc != N) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: TN needs ldc == N");
-    splits = d->splits ? d->splits : gemm_pick_splits(M, N, K, groups);
-    const int kps = ((K + splits - 1) / splits + 15) / 16 * 16;  // (gemm_launch rounds a split to whole 16-row slices)
-    // (only an override is judged: the update's own count stands as it is)
-    if (d->splits && (int64_t)(splits - 1) * kps >= K)
-      return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: a split would be empty");
-    const int64_t gmn = (int64_t)groups * M * N, gm = (int64_t)groups * M;
-    if (!d->workspace || (int64_t)splits * (gmn + gm) > d->workspace_floats)
-      return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: workspace too small");
-    p.b_rows = d->rows; p.splits = splits; p.kps = (K + splits - 1) / splits;
-    p.gc = (int64_t)M * N; p.ldc = N; p.part_stride = gmn;
-    p.C = d->workspace;
-    p.bias_part = d->workspace + (int64_t)splits * gmn;
-  } else {
-    if (layout != GEMM_NT && layout != GEMM_NN) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: layout is 0, 2 or 3");
-    if (d->splits > 1 || epi == EPI_PARTIAL) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: NT / NN are not split");
-    if ((epi == EPI_BIAS_TANH && layout != GEMM_NT) || (epi == EPI_DTANH && layout != GEMM_NN))
-      return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: epi 5 is an NT epilogue, epi 6 an NN one");
-    if ((epi == EPI_DELU || epi == EPI_DTANH) && !d->aux) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: epi 3 / 6 need aux");
-    if ((epi == EPI_BIAS || epi == EPI_BIAS_ELU || epi == EPI_BIAS_TANH) && !d->bias)
-      return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: epi 1 / 2 / 5 need bias");
-    p.C = d->C; p.ldc = d->ldc; p.gc = d->gc; p.bias = d->bias; p.gbias = d->gbias; p.a_rows = d->rows;
-  }
+  p.C = d->C; p.ldc = d->ldc; p.gc = d->gc; p.bias = d->bias; p.gbias = d->gbias; p.a_rows = d->rows;
+  k.p = p;  // (splits_out = 1)
   job = GemmJob{p, layout, epi, groups};
   return 0;
 }
 // the reduction of a TN descriptor's partials into its C (and db = bias)
-static void desc_reduce(const lrl_gemm_desc* d, const GemmJob& job, int splits, SegList& L) {
+static void desc_reduce(const lrl_gemm_desc* d, const GemmJob& job, const SplitK& k, SegList& L) {
   if (job.layout != GEMM_TN) return;
-  const int64_t gmn = (int64_t)d->groups * d->M * d->N, gm = (int64_t)d->groups * d->M;
-  L.s[L.n++] = Seg{d->workspace, d->C, gmn, gmn, splits, 1.f};
-  if (d->bias) L.s[L.n++] = Seg{job.p.bias_part, d->bias, gm, gm, splits, 1.f};
+  L.s[L.n++] = k.s[0];
+  if (d->bias) L.s[L.n++] = k.s[1];
 }
 
 extern "C" int32_t lrl_gemm_f32_ex(const lrl_gemm_desc* d, void* stream) {
   GemmJob job;
-  int splits = 1;
-  if (int32_t rc = desc_job(d, job, splits)) return rc;
+  SplitK k;
+  if (int32_t rc = desc_job(d, job, k)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   GemmP& p = job.p;
   const int layout = job.layout, epi = job.epi, groups = job.groups;
   if (layout == GEMM_TN) {
     if (int rc = gemm_launch(p, GEMM_TN, EPI_PARTIAL, groups, st)) return lrl_set_error(rc, "lrl_gemm_f32_ex: launch failed");
     SegList L{};
-    desc_reduce(d, job, splits, L);
+    desc_reduce(d, job, k, L);
     launch_seg(L, st);
   } else {
-    PlaneJob j{};
-    if (d->planes) {
-      j.W = d->B; j.ldw = d->ldb; j.gsrc = d->gb; j.groups = groups; j.trans = layout == GEMM_NN ? 1 : 0;
-      j.rows = layout == GEMM_NN ? d->K : d->N; j.cols = layout == GEMM_NN ? d->N : d->K;
-      j.dst = reinterpret_cast<uint16_t*>(d->workspace);
-      if (!d->workspace || plane_elems(j) > 2 * d->workspace_floats)
-        return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: workspace too small for the planes");
-      if (int rc = x6_planes_launch(&j, 1, st)) return lrl_set_error(rc, "lrl_gemm_f32_ex: planes launch failed");
-      gemm_use_planes(p, j);
-    }
+    if (d->planes)
+      if (int rc = use_test_planes(p, layout, groups, d->workspace, d->workspace_floats, st)) return rc;
     if (int rc = gemm_launch(p, layout, epi, groups, st))
       return lrl_set_error(rc, "lrl_gemm_f32_ex: bad layout/epilogue or launch failure");
     if (d->planes && (gemm_last_path() & 0xff) != FAM_X6P)
       return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_ex: shape not eligible for the x6p kernel");
   }
   if (d->path_out) *d->path_out = gemm_last_path();
-  if (d->splits_out) *d->splits_out = splits;
+  if (d->splits_out) *d->splits_out = k.p.splits;
   return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_gemm_f32_ex: launch failed");
 }
 
@@ -2154,18 +2096,18 @@ extern "C" int32_t lrl_gemm_f32_multi(const lrl_gemm_desc* d, int32_t n, void* s
   if (!d || n < 2 || n > MAX_MULTI_JOBS) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_multi: 2 or 3 descriptors");
   hipStream_t st = static_cast<hipStream_t>(stream);
   GemmJob jobs[MAX_MULTI_JOBS];
-  int splits[MAX_MULTI_JOBS];
+  SplitK ks[MAX_MULTI_JOBS];
   for (int i = 0; i < n; ++i) {
     if (d[i].planes) return lrl_set_error(LRL_E_INVALID, "lrl_gemm_f32_multi: no planes");
-    if (int32_t rc = desc_job(&d[i], jobs[i], splits[i])) return rc;
+    if (int32_t rc = desc_job(&d[i], jobs[i], ks[i])) return rc;
   }
   const int r = gemm_launch_multi(jobs, n, st);
   if (r < 0) return lrl_set_error(r, "lrl_gemm_f32_multi: launch failed");
   if (r == 0) return 1;  // not one of the sets on offer: nothing was launched
   SegList L{};
   for (int i = 0; i < n; ++i) {
-    desc_reduce(&d[i], jobs[i], splits[i], L);
-    if (d[i].splits_out) *d[i].splits_out = splits[i];
+    desc_reduce(&d[i], jobs[i], ks[i], L);
+    if (d[i].splits_out) *d[i].splits_out = ks[i].p.splits;
   }
   launch_seg(L, st);
   if (d[n - 1].path_out) *d[n - 1].path_out = gemm_last_path();

@@ -250,20 +250,23 @@ SWITCHES = [dict(LRL_PPO_BWD_MULTI="0", LRL_PPO_FORK=None), dict(LRL_PPO_BWD_MUL
             dict(LRL_PPO_BWD_MULTI=None, LRL_PPO_FORK=None)]
 
 
-def test_update_gradients_do_not_depend_on_the_backward_packing():
-    """The Mini Cheetah preset net, a 256-row minibatch: the packed backward tail (LRL_PPO_BWD_MULTI=1, and unset) leaves
-    the same bits as the eight-launch path with and without its stream fork — the whole flat gradient, ctrl's mb slots
-    and the whole workspace, the dhe1 / dhe2 rows and every partial slice included."""
+@pytest.mark.parametrize("num_obs,history,N,T", [(42, 630, 256, 4), (42, 630, 200, 4), (235, 3525, 256, 4)])
+def test_update_gradients_do_not_depend_on_the_backward_packing(num_obs, history, N, T):
+    """The packed backward tail (LRL_PPO_BWD_MULTI=1, and unset) leaves the same bits as the eight-launch path with and
+    without its stream fork — the whole flat gradient, ctrl's mb slots and the whole workspace, the dhe1 / dhe2 rows and
+    every partial slice included.  All settings launch the one collected job list, so the cases are the shapes at which
+    the ways of launching it can part: the Mini Cheetah preset net at a 256-row minibatch; at 200 rows (the last head
+    workgroup partial, row counts off the 64 / 128-row tiles, so jobs may fall out of the packed sets into launch_jobs'
+    one-by-one path); and the perceptive net (X pitch 256, the history padded 3525 -> 3536)."""
     from lrl.ppo.actor_critic import ActorCritic
     from lrl.ppo.ppo import PPO
-    N, T = 256, 4
-    ac = ActorCritic(42, 18, 630, 12)
+    ac = ActorCritic(num_obs, 18, history, 12)
     init_params(ac)
     alg = PPO(ac.cuda(), device=dev, fused=True)
-    alg.init_storage(N, T, [42], [18], [630], [12])
+    alg.init_storage(N, T, [num_obs], [18], [history], [12])
     _random_storage(alg)
     mb = N * T // 4
-    assert mb == 256
+    assert mb == N
     rows = torch.randperm(N * T, device=dev, generator=torch.Generator(device=dev).manual_seed(7))[:mb].contiguous()
     hist_ld = alg.storage.observation_histories.flatten(0, 1).stride(0)
     ref = _forward_backward(alg, ac, mb, rows, hist_ld, dict(LRL_PPO_BWD_MULTI="1", LRL_PPO_FORK=None))
