@@ -538,6 +538,92 @@ int32_t lrl_sim_set_terrain(lrl_sim* sim, const float* vertices, const int16_t* 
 int32_t lrl_sim_shift_history(lrl_sim* sim, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The navigation wrapper's step on the device (HighLevelControlWrapper(native=True), lrl/high_level.py; the
+ * reference's scripts/high_level_play.py:131-249): the wrapper's own per-env work and its reset batch around
+ * lrl_sim_step, without a host read.  The wrapper's buffers stay the caller's (torch tensors); lrl_nav_state carries
+ * their device pointers and the scalars, and is read on every call, so a caller may rebind any of them between steps.
+ * All [n, k] buffers are contiguous row-major, the two sum tables are [num_step_terms + num_terminal_terms + 1][n]
+ * with "total" as the last row (row r = term r of the list below).
+ * ------------------------------------------------------------------------------------------ */
+enum lrl_nav_term { /* high_level_play.py:339-363 */
+  LRL_NAV_R_DISTANCE = 0,              /* |last_pos_xy - goal| */
+  LRL_NAV_R_ACTION_RATE,               /* sum_k (last_actions_k - actions_k)^2 */
+  LRL_NAV_R_LATERAL_VEL,               /* lateral_vel^2 */
+  LRL_NAV_R_BACKWARD_VEL,              /* backward_vel^2 */
+  LRL_NAV_R_TERMINAL_DISTANCE_COVERED, /* dist_travelled */
+  LRL_NAV_R_TERMINAL_DISTANCE_GS,      /* goal reached (0 / 1) */
+  LRL_NAV_R_TERMINAL_LL_RESET,         /* the low-level env's reset flag, LRL_T_RESET (0 / 1) */
+  LRL_NAV_R_TERMINAL_TIME_OUT,         /* episode_length > max_episode_length (0 / 1) */
+  LRL_NAV_R_NUM
+};
+/* sizeof(lrl_nav_state) and the offsets lrl/_abi.py's mirror is checked against (tests/test_nav_native.py) */
+#define LRL_NAV_STATE_BYTES 424
+#define LRL_NAV_STATE_OFF_IDS 120
+#define LRL_NAV_STATE_OFF_PREV_LL 184
+#define LRL_NAV_STATE_OFF_N 192
+#define LRL_NAV_STATE_OFF_BASE_INIT_STATE 212
+#define LRL_NAV_STATE_OFF_TERM 224
+#define LRL_NAV_STATE_OFF_SCALE 320
+#define LRL_NAV_STATE_OFF_GOAL_THRESHOLD 420
+/* envs per workgroup of the per-env nav kernels: block_counts holds (n + LRL_NAV_BLOCK - 1) / LRL_NAV_BLOCK ints */
+#define LRL_NAV_BLOCK 256
+typedef struct lrl_nav_state {
+  float* obs_buf;              /* [n,14] base_pos, base_lin_vel, base_ang_vel, actions, goal */
+  float* rew_buf;              /* [n] */
+  uint8_t* reset_buf;          /* [n] bool bytes */
+  uint8_t* gs_buf;             /* [n] goal reached in this step */
+  uint8_t* time_buf;           /* [n] timed out in this step */
+  int32_t* episode_length_buf; /* [n] */
+  float* actions;              /* [n,3] the clamped, thresholded command of this step */
+  float* last_actions;         /* [n,3] */
+  float* last_pos;             /* [n,3] */
+  float* dist_travelled;       /* [n] */
+  float* lateral_vel;          /* [n] */
+  float* backward_vel;         /* [n] */
+  float* goal_position;        /* [n,2] */
+  float* episode_sums;         /* [terms+1][n] */
+  float* episode_sums_eval;    /* [terms+1][n]: the eval envs' first finished episode, -1 = none yet */
+  int32_t* ids;                /* [n] out: the step's reset env ids, ascending */
+  int32_t* count;              /* [1] out: their count */
+  int32_t* block_counts;       /* scratch, see LRL_NAV_BLOCK */
+  /* the step's logged means: fresh slots per step keep the values of earlier steps.  A group without a reset in
+   * the step receives prev_* (null: the slot is left as it is). */
+  float* means_train;          /* [terms+1] mean of each sum row over the reset train envs (id < num_train_envs) */
+  float* means_eval;           /* [terms+1] the same over the reset eval envs */
+  float* means_ll;             /* [rows of LRL_T_EPISODE_SUMS] the low-level env's episode logging of the batch */
+  const float* prev_train;
+  const float* prev_eval;
+  const float* prev_ll;
+  int32_t n, num_train_envs, max_episode_length;
+  int32_t num_step_terms, num_terminal_terms; /* together at most LRL_MAX_REWARD_TERMS */
+  float base_init_state[3];
+  int32_t term[LRL_MAX_REWARD_TERMS]; /* enum lrl_nav_term: the step terms in order, then the terminal terms */
+  float scale[LRL_MAX_REWARD_TERMS];  /* float32 of the python scale (step terms already x dt) */
+  float command_threshold;            /* 0.2: the xy command is multiplied by (|xy| > command_threshold) */
+  float goal_threshold;               /* 0.1: goal reached when |base_pos_xy - goal| < goal_threshold */
+} lrl_nav_state;
+/* step() :127-131: state->actions = clamp(actions, -2, 2) with the xy pair multiplied by (|xy| > command_threshold)
+ * (a product, so a zeroed command keeps its sign), and the sim's commands[:, :3] = state->actions.  One launch.
+ * `actions` [n,3] f32 device, contiguous. */
+int32_t lrl_nav_begin_step(lrl_sim* sim, const lrl_nav_state* state, const float* actions, void* stream);
+/* Everything of step() after ll_env.step (:133-140), in the reference's order: episode_length += 1;
+ * post_physics_step; check_termination (reset |= LRL_T_RESET | gs | time); compute_reward (the step terms in list
+ * order, the terminal terms for every env if and only if some env's reset flag is set, then "total"); the reset
+ * batch (ids and count; train-group means, eval first-episode bookkeeping and means, zeroing; the low-level env's
+ * episode logging as lrl_rows_mean_zero_dev and its reset as lrl_sim_reset_idx_dev with root_mode .. y_off; the
+ * history rows of the ids zeroed as HistoryWrapper.reset_idx does; the wrapper's per-env buffers of the ids zeroed and
+ * their reset flags cleared); compute_observations for every env from the post-reset state; last_pos, last_actions.
+ * Five launches: per-env flags and step terms; terminal terms, total and id compaction; the means (one workgroup
+ * per row: thread-stride partials and an LDS tree, a fixed order); the sim's reset kernel; observations and zeroing.
+ * step_flags: LRL_NAV_ONLY_FLAGS stops after the first two launches (ids and count are then final: a caller that must
+ * read the batch on the host before the sums are zeroed does so and calls again with LRL_NAV_ONLY_RESET for the
+ * rest); 0 runs everything. */
+#define LRL_NAV_ONLY_FLAGS 0x100u
+#define LRL_NAV_ONLY_RESET 0x200u
+int32_t lrl_nav_end_step(lrl_sim* sim, const lrl_nav_state* state, uint32_t step_flags, int32_t root_mode, float xy_lo,
+                         float xy_span, float x_off, float y_off, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Headless camera (gym.create_camera_sensor / render_all_camera_sensors / get_camera_image IMAGE_COLOR,
  * legged_robot.py:1301-1355): a ray caster over the sim's own collision model, one env per call.  What is drawn: the
  * base box (the span of the base's collision shapes), every collision sphere with a radius, and one capsule of radius

@@ -702,6 +702,56 @@ int32_t lrl_sim_env_lists(lrl_sim* s, int32_t mode, int32_t interval, int32_t* i
   return 0;
 }
 
+// What lrl_nav_begin_step / lrl_nav_end_step refuse: the kernels index every buffer by env id < n and every table by
+// row < terms + 1, so these are the bounds they rely on.
+static int nav_check(const lrl_sim* s, const lrl_nav_state* v, const char* who) {
+  if (!s || !v) return fail(LRL_E_INVALID, "%s: null sim or state", who);
+  const void* ptr[] = {v->obs_buf, v->rew_buf, v->reset_buf, v->gs_buf, v->time_buf, v->episode_length_buf, v->actions,
+                       v->last_actions, v->last_pos, v->dist_travelled, v->lateral_vel, v->backward_vel,
+                       v->goal_position, v->episode_sums, v->episode_sums_eval, v->ids, v->count, v->block_counts,
+                       v->means_train, v->means_eval, v->means_ll};
+  static const char* const name[] = {"obs_buf", "rew_buf", "reset_buf", "gs_buf", "time_buf", "episode_length_buf",
+                                     "actions", "last_actions", "last_pos", "dist_travelled", "lateral_vel",
+                                     "backward_vel", "goal_position", "episode_sums", "episode_sums_eval", "ids",
+                                     "count", "block_counts", "means_train", "means_eval", "means_ll"};
+  for (size_t i = 0; i < sizeof(ptr) / sizeof(ptr[0]); ++i)
+    if (!ptr[i]) return fail(LRL_E_INVALID, "%s: lrl_nav_state.%s is null", who, name[i]);
+  if (v->n != s->S.n) return fail(LRL_E_INVALID, "%s: lrl_nav_state.n %d, the sim has %d envs", who, v->n, s->S.n);
+  if (v->num_train_envs < 1 || v->num_train_envs > v->n)
+    return fail(LRL_E_INVALID, "%s: num_train_envs %d outside [1, %d]", who, v->num_train_envs, v->n);
+  if (v->num_step_terms < 0 || v->num_terminal_terms < 0 ||
+      v->num_step_terms + (int64_t)v->num_terminal_terms > LRL_MAX_REWARD_TERMS)
+    return fail(LRL_E_INVALID, "%s: %d step and %d terminal terms, at most %d together", who, v->num_step_terms,
+                v->num_terminal_terms, LRL_MAX_REWARD_TERMS);
+  for (int i = 0; i < v->num_step_terms + v->num_terminal_terms; ++i)
+    if (v->term[i] < 0 || v->term[i] >= LRL_NAV_R_NUM)
+      return fail(LRL_E_INVALID, "%s: term[%d] = %d is no lrl_nav_term", who, i, v->term[i]);
+  return 0;
+}
+
+int32_t lrl_nav_begin_step(lrl_sim* s, const lrl_nav_state* v, const float* actions, void* stream) {
+  if (int rc = nav_check(s, v, "lrl_nav_begin_step")) return rc;
+  if (!actions) return fail(LRL_E_INVALID, "lrl_nav_begin_step: null actions");
+  HIPCHECK(lrl_launch_nav_begin(&s->S, v, actions, (hipStream_t)stream));
+  return 0;
+}
+
+int32_t lrl_nav_end_step(lrl_sim* s, const lrl_nav_state* v, uint32_t step_flags, int32_t root_mode, float xy_lo,
+                         float xy_span, float x_off, float y_off, void* stream) {
+  if (int rc = nav_check(s, v, "lrl_nav_end_step")) return rc;
+  if (root_mode < 0 || root_mode > 2) return fail(LRL_E_INVALID, "lrl_nav_end_step: root_mode %d", root_mode);
+  if ((step_flags & ~(LRL_NAV_ONLY_FLAGS | LRL_NAV_ONLY_RESET)) ||
+      step_flags == (LRL_NAV_ONLY_FLAGS | LRL_NAV_ONLY_RESET))
+    return fail(LRL_E_INVALID, "lrl_nav_end_step: step_flags 0x%x", step_flags);
+  hipStream_t st = (hipStream_t)stream;
+  if (!(step_flags & LRL_NAV_ONLY_RESET)) HIPCHECK(lrl_launch_nav_flags(&s->S, v, st));
+  if (step_flags & LRL_NAV_ONLY_FLAGS) return 0;
+  HIPCHECK(lrl_launch_nav_log(&s->S, v, s->hk.n_es, st));
+  HIPCHECK(lrl_launch_reset(s->dk, &s->S, v->ids, v->n, v->count, root_mode, xy_lo, xy_span, x_off, y_off, 0, st));
+  HIPCHECK(lrl_launch_nav_finish(&s->S, v, s->hk.p.num_history * s->hk.p.num_obs, st));
+  return 0;
+}
+
 int32_t lrl_sim_terrain_curriculum(lrl_sim* s, const int32_t* ids, int32_t n, int64_t* levels, const int64_t* types,
                                    const int64_t* rand_levels, const float* terrain_origins, int32_t rows,
                                    int32_t cols, float half_env_length, float episode_length_s, int32_t max_level,

@@ -55,4 +55,9 @@ hipError_t lrl_launch_metrics(const KParams*, const KState*, const KMetrics*, in
 hipError_t lrl_launch_metrics_clear(const KState*, const KMetrics*, hipStream_t);
 hipError_t lrl_launch_metrics_reduce(const KParams*, const KState*, const KMetrics*, int32_t, int32_t, double*,
                                      hipStream_t);
+// lrl_nav.hip (hist_floats: one env's row of the observation history)
+hipError_t lrl_launch_nav_begin(const KState*, const lrl_nav_state*, const float*, hipStream_t);
+hipError_t lrl_launch_nav_flags(const KState*, const lrl_nav_state*, hipStream_t);
+hipError_t lrl_launch_nav_log(const KState*, const lrl_nav_state*, int32_t, hipStream_t);
+hipError_t lrl_launch_nav_finish(const KState*, const lrl_nav_state*, int32_t, hipStream_t);
 }

@@ -148,6 +148,26 @@ class LrlDevCurriculum(C.Structure):
                 ("draws", C.c_void_p), ("env_bins_f_prev", C.c_void_p), ("command_area_prev", C.c_void_p)]
 
 
+# enum lrl_nav_term (include/lrl.h): the navigation wrapper's reward names in id order
+NAV_TERMS = ("distance", "action_rate", "lateral_vel", "backward_vel", "terminal_distance_covered",
+             "terminal_distance_gs", "terminal_ll_reset", "terminal_time_out")
+NAV_ONLY_FLAGS, NAV_ONLY_RESET = 0x100, 0x200
+NAV_BLOCK = 256  # LRL_NAV_BLOCK
+
+
+class LrlNavState(C.Structure):
+    """lrl_nav_state (lrl_nav_begin_step / lrl_nav_end_step): the navigation wrapper's buffers and scalars."""
+    _fields_ = [(k, C.c_void_p) for k in ("obs_buf", "rew_buf", "reset_buf", "gs_buf", "time_buf", "episode_length_buf",
+                                          "actions", "last_actions", "last_pos", "dist_travelled", "lateral_vel",
+                                          "backward_vel", "goal_position", "episode_sums", "episode_sums_eval", "ids",
+                                          "count", "block_counts", "means_train", "means_eval", "means_ll",
+                                          "prev_train", "prev_eval", "prev_ll")] + \
+               [(k, i32) for k in ("n", "num_train_envs", "max_episode_length", "num_step_terms",
+                                   "num_terminal_terms")] + \
+               [("base_init_state", f32 * 3), ("term", i32 * MAX_REWARD_TERMS), ("scale", f32 * MAX_REWARD_TERMS),
+                ("command_threshold", f32), ("goal_threshold", f32)]
+
+
 class LrlGemmDesc(C.Structure):
     """lrl_gemm_desc (lrl_gemm_f32_ex): a product in the update's grouped / pitched operand forms."""
     _fields_ = [(k, i32) for k in ("layout", "epi", "M", "N", "K", "groups", "planes", "splits")] + \
@@ -211,7 +231,7 @@ _lib = None
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 # the files and order of csrc/Makefile's SRC_HASH (SRCS then HDRS)
 _HASHED = ["lrl_env_dispatch.hip", "lrl_aux.hip", "lrl_gae.hip", "lrl_gemm.hip", "lrl_ppo.hip", "lrl_capi.cpp", "lrl_curriculum.cpp",
-           "lrl_curriculum_dev.hip", "lrl_env_flat.hip", "lrl_render.hip", "lrl_env_mesh_tgs.hip", "lrl_metrics.hip", "lrl_env_mesh.hip", "lrl_kparams.h", "lrl_gemm.h", "../../include/lrl.h", "../../include/lrl_philox.h",
+           "lrl_curriculum_dev.hip", "lrl_env_flat.hip", "lrl_render.hip", "lrl_env_mesh_tgs.hip", "lrl_metrics.hip", "lrl_env_mesh.hip", "lrl_nav.hip", "lrl_kparams.h", "lrl_gemm.h", "../../include/lrl.h", "../../include/lrl_philox.h",
            "lrl_env_layout.h", "lrl_env_step.h", "lrl_launch.h", "Makefile"]  # (the build flags too: a library built with other flags is stale)
 
 
@@ -256,8 +276,12 @@ def lib():
                      "lrl_rows_mean_zero_dev", "lrl_sim_curriculum_resample_dev", "lrl_debug_gemm_paths",
                      "lrl_debug_sim_garbage", "lrl_debug_sim_arena", "lrl_sim_render", "lrl_sim_record",
                      "lrl_debug_sim_lds_bytes", "lrl_sim_metrics_enable", "lrl_sim_metrics_clear",
-                     "lrl_sim_metrics_tensors", "lrl_sim_metrics_reduce"]:
+                     "lrl_sim_metrics_tensors", "lrl_sim_metrics_reduce", "lrl_nav_begin_step",
+                     "lrl_nav_end_step"]:
             getattr(L, name).restype = C.c_int32
+        L.lrl_nav_begin_step.argtypes = [C.c_void_p, C.POINTER(LrlNavState), C.c_void_p, C.c_void_p]
+        L.lrl_nav_end_step.argtypes = [C.c_void_p, C.POINTER(LrlNavState), C.c_uint32, C.c_int32, C.c_float, C.c_float,
+                                       C.c_float, C.c_float, C.c_void_p]
         L.lrl_np_sum_f64.restype = C.c_double
         L.lrl_np_sum_f64.argtypes = [C.c_void_p, C.c_int64]
         L.lrl_ppo_workspace_bytes.restype = C.c_int64

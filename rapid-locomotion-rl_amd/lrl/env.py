@@ -132,6 +132,19 @@ class _LazyExtras(dict):
             self[k] = v
 
 
+def _logged_prev(extras, key, names, prev, last):
+    """The ``prev`` slot of a reset batch logged on the device (an empty batch republishes it): what the host path
+    logged under extras[key] since ``last``, the dict the device path published last, as a fresh tensor (published
+    slots are never rewritten); else ``prev``.  Returns (prev, whether the key is already in the dict)."""
+    host = dict.get(extras, key)
+    if host is None or host is last:
+        return prev, host is not None
+    vals = [host.get("rew_" + k) for k in names]
+    if all(isinstance(v, torch.Tensor) and v.numel() == 1 for v in vals):
+        prev = torch.stack([v.reshape(()).to(prev.device, torch.float32) for v in vals])
+    return prev, True
+
+
 class _Upload:
     """Host -> device staging through pinned buffers: each put() packs numpy arrays into one pinned slot and issues one
     non-blocking copy on the current stream, returning typed device views of it.  A ring of slots, each rewritten only
@@ -403,6 +416,9 @@ class LeggedRobotEnv:
             and self._track_rows is not None and len(self._curriculum.keys) == 3
         self._dcur = None      # device curriculum buffers (allocated at the first device step)
         self._dev_auth = False  # True: the device copy of the curriculum / env bins is the current one
+        # reset batches logged on the device under the navigation wrapper (_publish_reset_batch_dev): whether
+        # "train/episode" is out, the dict published last, the command bins uploaded last
+        self._nav_log = {"seen": False, "ep": None, "bins": None}
         self.init_done = True
 
     # ------------------------------------------------------------- command curriculum state (host mirror of the device)
@@ -919,6 +935,42 @@ class LeggedRobotEnv:
         if self.record_now:  # (record_eval_now: this path has no eval group)
             self._record_frame("train")
         return self.obs_buf, self.rew_buf, self._reset_u8.view(torch.bool), self.extras
+
+    def _publish_reset_batch_dev(self, means):
+        """reset_idx's extras (legged_robot.py:261-290) for a reset batch of the fork path whose episode logging and
+        reset ran on the device (lrl_nav_end_step, lrl/high_level.py): ``means`` is the step's own slot, holding the
+        batch's means or, for an empty batch, the previous ones, so the key appears with the first batch (decided on
+        access, as in _step_device)."""
+        ex, cfg = self.extras, self.cfg
+        c = cfg.commands
+        self._due_next = None
+        self._sums_host = None
+        d = self._nav_log
+        ep = {"rew_" + k: m for k, m in zip(self.episode_sums, means.unbind(0))}
+        if c.command_curriculum:
+            bins = self.env_command_bins
+            if d["bins"] is None or not np.array_equal(d["bins"], bins):
+                if self.env_command_bins_t.shape != (self.num_envs,):
+                    self.env_command_bins_t = torch.zeros(self.num_envs, device=self.device)
+                self.env_command_bins_t.copy_(self._up.put(bins.astype(np.float32))[0])
+                d["bins"] = bins.copy()
+            ex["env_bins"] = self.env_command_bins_t[:self.num_train_envs]
+            ep["command_area"] = np.sum(self.curriculum.weights) / self.curriculum.weights.shape[0]
+        if c.yaw_command_curriculum:
+            ep["max_command_yaw"] = cfg.command_ranges["ang_vel_yaw"][1]
+        if d["seen"] or dict.get(ex, "train/episode") is not None:
+            d["seen"] = True
+            ex["train/episode"] = ep
+        else:
+            def seen(m0=means[0]):
+                if bool(torch.isnan(m0).item()):
+                    return False
+                d["seen"] = True
+                return True
+            ex.set_conditional("train/episode", ep, seen)
+        d["ep"] = ep
+        if cfg.env.send_timeouts:
+            ex["time_outs"] = self.time_out_buf[:self.num_train_envs]
 
     def kernel_timing(self, start):
         """Env-kernel launch time, the one definition bench.py and the scripts use: HIP events around each

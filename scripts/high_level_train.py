@@ -9,10 +9,12 @@ run's ``checkpoints/ac_weights_last.pt``) or an ``.npz`` holding the same tensor
 ``--timing K`` runs K iterations after one warm-up iteration and prints one JSON line: ms per iteration, split into
 the rollout (200 wrapper steps, each a low-level policy act and env step plus the wrapper's torch) and the update,
 and the update's share of the split-bf16 MFMA bound of its GEMM FLOPs.  ``--fused 0`` trains with the torch-autograd
-update instead of the native one (the comparison the timing is for).
+update instead of the native one (the comparison the timing is for).  ``--native 1`` runs the wrapper's own step on
+the device (``HighLevelControlWrapper(native=True)``: six launches per step and no host read, in place of the wrapper's
+torch); the default is the host-torch wrapper.
 
 usage: python scripts/high_level_train.py LOW_LEVEL_CHECKPOINT [--iterations N] [--num-envs N] [--steps T]
-                                          [--robot go1|mc] [--root DIR] [--fused 0|1] [--timing K]"""
+                                          [--robot go1|mc] [--root DIR] [--fused 0|1] [--native 0|1] [--timing K]"""
 import argparse
 import json
 import os
@@ -90,6 +92,7 @@ if __name__ == "__main__":
     ap.add_argument("--robot", default="go1", choices=["go1", "mc"])
     ap.add_argument("--root", default=None, help="run root (default: <package>/high_level_policy/runs)")
     ap.add_argument("--fused", type=int, default=1, choices=[0, 1], help="0: the torch-autograd update")
+    ap.add_argument("--native", type=int, default=0, choices=[0, 1], help="1: the wrapper's step on the device")
     ap.add_argument("--timing", type=int, default=0, help="time this many iterations and print one JSON line")
     a = ap.parse_args()
 
@@ -99,7 +102,7 @@ if __name__ == "__main__":
     from ml_logger import logger
 
     env = HighLevelControlWrapper.from_actor_critic(load_low_level(a.low_level), num_envs=a.num_envs, device="cuda:0",
-                                                    robot=a.robot)
+                                                    robot=a.robot, native=bool(a.native))
     stem = Path(__file__).stem
     logger.configure(logger.utcnow(f"rapid-locomotion/%Y-%m-%d/{stem}/%H%M%S.%f"),
                      root=Path(a.root or f"{HLP_ROOT_DIR}/high_level_policy/runs").resolve())
@@ -115,6 +118,7 @@ if __name__ == "__main__":
         ms_iter, ms_update = timed_learn(runner, a.timing, eval_freq=200, eval_expert=True)
         flops = update_gemm_flops(runner)
         print(json.dumps(dict(workload=f"{a.num_envs} envs x {runner.num_steps_per_env} steps", fused=bool(a.fused),
+                              native=bool(a.native),
                               iterations=a.timing, ms_per_iteration=round(ms_iter, 2),
                               ms_rollout=round(ms_iter - ms_update, 2), ms_update=round(ms_update, 2),
                               update_gemm_gflop=round(flops / 1e9, 2),
