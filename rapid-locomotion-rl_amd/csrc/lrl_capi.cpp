@@ -931,6 +931,25 @@ int32_t lrl_sim_record(lrl_sim* s, int32_t env, const lrl_camera* cam, uint8_t* 
   return 0;
 }
 
+int32_t lrl_sim_depth(lrl_sim* s, const lrl_depth_camera* cam, int32_t first_env, int32_t num_envs, int32_t only_reset,
+                      float* depth, int32_t* ids, void* stream) {
+  if (!s) return fail(LRL_E_INVALID, "null sim");
+  if (!cam) return fail(LRL_E_INVALID, "lrl_sim_depth: null camera");
+  if (!depth) return fail(LRL_E_INVALID, "lrl_sim_depth: null depth buffer");
+  if (first_env < 0 || num_envs < 0 || first_env > s->S.n || num_envs > s->S.n - first_env)
+    return fail(LRL_E_INVALID, "env range [%d, %d + %d) outside the sim's %d envs", first_env, first_env, num_envs, s->S.n);
+  if (cam->width < 1 || cam->width > 1024 || cam->height < 1 || cam->height > 1024)
+    return fail(LRL_E_INVALID, "depth image size %d x %d outside [1, 1024]", cam->width, cam->height);
+  if (!(cam->hfov_deg > 1.f && cam->hfov_deg < 179.f)) return fail(LRL_E_INVALID, "hfov_deg %g outside (1, 179)", cam->hfov_deg);
+  if (!(cam->near >= 0.f && cam->near < cam->far && cam->far < 3.0e38f))
+    return fail(LRL_E_INVALID, "near %g, far %g outside 0 <= near < far < 3e38", cam->near, cam->far);
+  if (!(fabsf(cam->pitch_deg) < 90.f)) return fail(LRL_E_INVALID, "|pitch_deg| %g >= 90", cam->pitch_deg);
+  if (s->hk.p.terrain_mesh && !s->hk.terr_vtx) return fail(LRL_E_INVALID, "terrain_mesh set but no lrl_sim_set_terrain");
+  HIPCHECK(lrl_launch_rigid_body(s->dk, &s->S, s->d_body_leg, s->d_body_link, s->d_foot_xyz, (hipStream_t)stream));
+  HIPCHECK(lrl_launch_depth(s->dk, &s->S, &s->rt, cam, first_env, num_envs, only_reset, depth, ids, (hipStream_t)stream));
+  return 0;
+}
+
 int32_t lrl_sim_shift_history(lrl_sim* s, void* stream) {
   if (!s) return fail(LRL_E_INVALID, "null sim");
   HIPCHECK(lrl_launch_shift_history(&s->S, s->hk.p.num_obs, s->hk.p.num_history * s->hk.p.num_obs, 1,

@@ -204,6 +204,16 @@ RENDER_SPHERE = (0.95, 0.75, 0.15)
 RENDER_LINK = (0.20, 0.35, 0.80)
 
 
+class LrlDepthCamera(C.Structure):
+    """lrl_depth_camera (lrl_sim_depth): the base-mounted depth camera every env carries."""
+    _fields_ = [("pos", f32 * 3), ("pitch_deg", f32), ("hfov_deg", f32), ("near", f32), ("far", f32), ("width", i32),
+                ("height", i32), ("flags", u32)]
+
+
+# the LRL_DEPTH_* defines of include/lrl.h (tests/test_depth_abi.py compares)
+DEPTH_NO_ROBOT = 1
+
+
 PPO_CTRL_BYTES = 64  # sizeof(lrl_ppo_ctrl): double lr, double loss_sum[3], float mb[4], float x4
 
 
@@ -231,8 +241,8 @@ _lib = None
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 # the files and order of csrc/Makefile's SRC_HASH (SRCS then HDRS)
 _HASHED = ["lrl_env_dispatch.hip", "lrl_aux.hip", "lrl_gae.hip", "lrl_gemm.hip", "lrl_ppo.hip", "lrl_capi.cpp", "lrl_curriculum.cpp",
-           "lrl_curriculum_dev.hip", "lrl_env_flat.hip", "lrl_render.hip", "lrl_env_mesh_tgs.hip", "lrl_metrics.hip", "lrl_env_mesh.hip", "lrl_nav.hip", "lrl_kparams.h", "lrl_gemm.h", "../../include/lrl.h", "../../include/lrl_philox.h",
-           "lrl_env_layout.h", "lrl_env_step.h", "lrl_launch.h", "Makefile"]  # (the build flags too: a library built with other flags is stale)
+           "lrl_curriculum_dev.hip", "lrl_env_flat.hip", "lrl_render.hip", "lrl_env_mesh_tgs.hip", "lrl_metrics.hip", "lrl_env_mesh.hip", "lrl_nav.hip", "lrl_depth.hip", "lrl_kparams.h", "lrl_gemm.h", "../../include/lrl.h", "../../include/lrl_philox.h",
+           "lrl_env_layout.h", "lrl_env_step.h", "lrl_launch.h", "lrl_raycast.h", "Makefile"]  # (the build flags too: a library built with other flags is stale)
 
 
 def source_hash():
@@ -277,8 +287,10 @@ def lib():
                      "lrl_debug_sim_garbage", "lrl_debug_sim_arena", "lrl_sim_render", "lrl_sim_record",
                      "lrl_debug_sim_lds_bytes", "lrl_sim_metrics_enable", "lrl_sim_metrics_clear",
                      "lrl_sim_metrics_tensors", "lrl_sim_metrics_reduce", "lrl_nav_begin_step",
-                     "lrl_nav_end_step"]:
+                     "lrl_nav_end_step", "lrl_sim_depth"]:
             getattr(L, name).restype = C.c_int32
+        L.lrl_sim_depth.argtypes = [C.c_void_p, C.POINTER(LrlDepthCamera), C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]
         L.lrl_nav_begin_step.argtypes = [C.c_void_p, C.POINTER(LrlNavState), C.c_void_p, C.c_void_p]
         L.lrl_nav_end_step.argtypes = [C.c_void_p, C.POINTER(LrlNavState), C.c_uint32, C.c_int32, C.c_float, C.c_float,
                                        C.c_float, C.c_float, C.c_void_p]

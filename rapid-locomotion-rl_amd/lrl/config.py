@@ -144,6 +144,28 @@ def make_cfg():
 
 Cfg = make_cfg()
 
+# The egocentric depth camera's group (project-only: the reference has no such sensor, so the defaults above do not
+# hold it and vars(Cfg) / to_dict() are the reference's; add_depth_camera installs it).
+_DEPTH = dict(width=64, height=48, hfov_deg=87.0, pos=[0.27, 0.0, 0.03], pitch_deg=20.0, near=0.05, far=3.0,
+              update_interval=5, see_robot=True)
+
+
+def add_depth_camera(cfg, **overrides):
+    """Install ``cfg.depth``: every env of a ``LeggedRobotEnv`` built from ``cfg`` then carries a depth camera bolted
+    to its base (``env.depth_images``, lrl_sim_depth).  Fields: ``width`` x ``height`` pixels, ``hfov_deg``, the mount
+    point ``pos`` in the base frame, ``pitch_deg`` about the base's y axis (positive looks down), the ``near`` / ``far``
+    clamps in metres, ``update_interval`` (env steps between full refreshes; an env that was reset is redrawn at once)
+    and ``see_robot`` (False: the env's own body is not drawn).
+
+    The defaults are choices modelled on a trunk-mounted RealSense-class sensor read at 10 Hz (64 x 48 after
+    downsampling, 87 degree horizontal field of view, a 3 m working range, every 5th 50 Hz policy step); they are not
+    measurements of any robot or camera.  ``overrides`` replace them; an unknown key is an error."""
+    unknown = set(overrides) - set(_DEPTH)
+    if unknown:
+        raise KeyError(f"add_depth_camera: unknown field(s) {sorted(unknown)}; known: {', '.join(_DEPTH)}")
+    cfg.depth = _build(dict(_DEPTH, **overrides), "depth")
+    return cfg
+
 _LEG_ORDER = ("FL", "RL", "FR", "RR")
 
 

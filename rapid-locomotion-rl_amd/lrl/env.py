@@ -368,6 +368,24 @@ class LeggedRobotEnv:
         if cfg.env.record_video:
             # (horizontal_fov: gymapi.CameraProperties' default; far_plane bounds the ray caster's reach)
             self.camera_props = Section(width=360, height=240, horizontal_fov=90.0, far_plane=100.0)
+        # egocentric depth camera (the project-only group Cfg.depth, lrl.config.add_depth_camera): one image per env
+        # from a camera on the base, redrawn at the end of step().  Without the group: no attribute, buffer or launch.
+        self._depth_cam = None
+        dc = getattr(cfg, "depth", None)
+        if dc is not None:
+            if int(dc.update_interval) < 1:
+                raise ValueError(f"Cfg.depth.update_interval must be >= 1, got {dc.update_interval}")
+            cam = _abi.LrlDepthCamera()
+            cam.pos[:] = [float(x) for x in dc.pos]
+            cam.pitch_deg, cam.hfov_deg = float(dc.pitch_deg), float(dc.hfov_deg)
+            cam.near, cam.far = float(dc.near), float(dc.far)
+            cam.width, cam.height = int(dc.width), int(dc.height)
+            cam.flags = 0 if dc.see_robot else _abi.DEPTH_NO_ROBOT
+            self._depth_cam = cam
+            self._depth_interval = int(dc.update_interval)
+            self._depth_step = 0  # steps taken with the sensor: a full refresh when it is a multiple of the interval
+            self.depth_images = torch.full((self.num_envs, max(cam.height, 0), max(cam.width, 0)), cam.far,
+                                           dtype=torch.float32, device=self.device)
 
         # ---- origins, DR draws at creation (legged_robot.py:1216-1231, 1385-1415, 519-542) ----
         self._set_env_origins()
@@ -783,6 +801,8 @@ class LeggedRobotEnv:
             self._record_frame("train")
         if self.record_eval_now:
             self._record_frame("eval")
+        if self._depth_cam is not None:
+            self._depth_tick()
         return self.obs_buf, self.rew_buf, self._reset_u8.view(torch.bool), self.extras
 
     # rows of lrl_sim_extras_snapshot (include/lrl.h LRL_EXTRAS_*): key -> (first row, rows)
@@ -934,6 +954,8 @@ class LeggedRobotEnv:
         self._register_extras(ex)
         if self.record_now:  # (record_eval_now: this path has no eval group)
             self._record_frame("train")
+        if self._depth_cam is not None:
+            self._depth_tick()
         return self.obs_buf, self.rew_buf, self._reset_u8.view(torch.bool), self.extras
 
     def _publish_reset_batch_dev(self, means):
@@ -1041,6 +1063,30 @@ class LeggedRobotEnv:
         (height, width, 4) image (the camera sensor's IMAGE_COLOR)."""
         assert mode == "rgb_array"
         return self.render_images(0)[0].cpu().numpy()
+
+    def _depth_launch(self, only_reset, ids=None):
+        _abi.check(self._L.lrl_sim_depth(self._sim, C.byref(self._depth_cam), 0, self.num_envs, int(only_reset),
+                                         C.c_void_p(self.depth_images.data_ptr()),
+                                         C.c_void_p(ids.data_ptr()) if ids is not None else None, self._stream()))
+
+    def _depth_tick(self):
+        """The depth camera's part of step(), after the step's resets and re-observation: every update_interval-th
+        step (the first one included) redraws every env's image; the steps between redraw only the envs whose reset
+        flag is set, so no env shows its previous episode's view.  Two launches on the step's stream, no host read."""
+        self._depth_launch(only_reset=self._depth_step % self._depth_interval != 0)
+        self._depth_step += 1
+
+    def render_depth(self, ids=False):
+        """Redraw every env's depth image from the current state now (whatever the update interval) and return
+        (``depth_images``, ids): the planar depth in metres, float32 [num_envs, H, W], clamped to Cfg.depth's
+        [near, far] (``far`` where nothing is hit within it), and, with ``ids=True``, the int32 [num_envs, H, W] image of
+        what each pixel hit (include/lrl.h: 0 nothing, 1 ground, 2 the base box, 3 + s a collision sphere, then the link
+        capsules), else None.  Device tensors; ``depth_images`` is the env's own buffer, rewritten in place."""
+        if self._depth_cam is None:
+            raise RuntimeError("no depth camera: the cfg has no depth group (lrl.config.add_depth_camera)")
+        idt = torch.empty(self.depth_images.shape, dtype=torch.int32, device=self.device) if ids else None
+        self._depth_launch(only_reset=False, ids=idt)
+        return self.depth_images, idt
 
     def reset(self):
         """VelocityTrackingEasyEnv.reset (:66-69): reset all, then one zero-action step."""

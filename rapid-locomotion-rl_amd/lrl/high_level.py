@@ -46,6 +46,13 @@ class HighLevelControlWrapper:
         """ll_env: a HistoryWrapper over LeggedRobotEnv; low_level_policy: obs dict -> joint actions.
         native: run ``step`` on the device (refused, never replaced by the host path, where it cannot)."""
         self.native = bool(native)
+        if getattr(getattr(getattr(ll_env, "env", ll_env), "cfg", None), "depth", None) is not None:
+            # Both paths go through LeggedRobotEnv.step, whose depth refresh follows the step's own resets; this wrapper
+            # resets the low-level envs after that step (reset_idx / lrl_nav_end_step), so a reset env would keep its
+            # previous episode's image until its next redraw.  Refused rather than served stale.
+            raise ValueError("HighLevelControlWrapper: the low-level env's cfg has the depth camera group Cfg.depth; "
+                             "the wrapper resets envs after the low-level step's depth refresh, so the images of reset "
+                             "envs would be stale (not supported yet)")
         if self.native:
             self._native_check(ll_env, num_envs)
         self.ll_env = ll_env

@@ -8,8 +8,11 @@ the actor (``ActorCritic.act_student_fused``, the native GEMM chain).  A constan
 ``--steps`` policy steps after 20 zero-action steps, as play_mc does; the measured forward velocity is printed
 (and plotted with ``--plot out.png``).  ``--video OUT`` writes one frame of env 0 per policy step (the headless
 camera of ``env.render()``: the collision model plus link capsules) as ``OUT.npz``, and ``OUT.gif`` when PIL is installed.
+``--depth OUT`` gives every env the egocentric depth camera (lrl.config.add_depth_camera's defaults) and saves env 0's
+image after every policy step as ``OUT.npz``: ``depth`` float32 [T, H, W], metres.
 
   python scripts/play.py [--robot mc|go1] [--weights ac_weights.pt] [--envs 64] [--steps 1000] [--vx 1.0] [--video OUT]
+                         [--depth OUT]
 """
 import argparse
 import json
@@ -28,7 +31,7 @@ from lrl.history import HistoryWrapper  # noqa: E402
 from lrl.ppo.actor_critic import ActorCritic  # noqa: E402
 
 
-def load_env(robot, num_envs, device):
+def load_env(robot, num_envs, device, depth=False):
     cfg = lcfg.make_cfg()
     (lcfg.config_mini_cheetah if robot == "mc" else lcfg.config_go1)(cfg)
     dr = cfg.domain_rand
@@ -40,6 +43,8 @@ def load_env(robot, num_envs, device):
         cfg.sim.physx.solver_type = int(os.environ["LRL_SOLVER_TYPE"])
     cfg.terrain.num_rows, cfg.terrain.num_cols, cfg.terrain.border_size = 3, 5, 0
     cfg.terrain.max_init_terrain_level = min(cfg.terrain.max_init_terrain_level, cfg.terrain.num_rows - 1)
+    if depth:
+        lcfg.add_depth_camera(cfg)
     return HistoryWrapper(LeggedRobotEnv(device, cfg=cfg)), cfg
 
 
@@ -56,9 +61,11 @@ def load_policy(weights, cfg, device):
     return lambda ob: ac.act_student_fused(ob["obs"].contiguous(), ob["obs_history"])[0]
 
 
-def play(robot="mc", weights=None, num_envs=64, steps=1000, vx=1.0, vy=0.0, wz=0.0, device="cuda:0", frames=None):
-    """``frames``: a list that receives env 0's rendered frame (numpy uint8 [240, 360, 4]) after every policy step."""
-    env, cfg = load_env(robot, num_envs, device)
+def play(robot="mc", weights=None, num_envs=64, steps=1000, vx=1.0, vy=0.0, wz=0.0, device="cuda:0", frames=None,
+         depth=None):
+    """``frames``: a list that receives env 0's rendered frame (numpy uint8 [240, 360, 4]) after every policy step;
+    ``depth``: a list that receives env 0's depth image (numpy float32 [H, W]) after every policy step."""
+    env, cfg = load_env(robot, num_envs, device, depth=depth is not None)
     policy = load_policy(weights, cfg, device)
     e = env.env
 
@@ -82,6 +89,8 @@ def play(robot="mc", weights=None, num_envs=64, steps=1000, vx=1.0, vy=0.0, wz=0
         vel[i, :, 2] = e.base_ang_vel[:, 2].cpu().numpy()
         if frames is not None:
             frames.append(e.render())
+        if depth is not None:
+            depth.append(e.depth_images[0].cpu().numpy())
     upright = (e.projected_gravity[:, 2] < -0.8).float().mean().item()
     e.close()
     return vel, upright, e.dt
@@ -96,9 +105,13 @@ def main():
     ap.add_argument("--vx", type=float, default=1.0)
     ap.add_argument("--plot", default=None)
     ap.add_argument("--video", default=None, metavar="OUT", help="write env 0's frames to OUT.npz (and OUT.gif)")
+    ap.add_argument("--depth", default=None, metavar="OUT", help="write env 0's depth images to OUT.npz")
     a = ap.parse_args()
     frames = [] if a.video else None
-    vel, upright, dt = play(a.robot, a.weights, a.envs, a.steps, a.vx, frames=frames)
+    depth = [] if a.depth else None
+    vel, upright, dt = play(a.robot, a.weights, a.envs, a.steps, a.vx, frames=frames, depth=depth)
+    if a.depth:
+        np.savez_compressed(os.path.splitext(a.depth)[0] + ".npz", depth=np.stack(depth).astype(np.float32))
     if a.video:
         from ml_logger import ML_Logger
         out = os.path.abspath(os.path.splitext(a.video)[0])
