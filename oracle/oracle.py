@@ -121,16 +121,18 @@ def env_step(model, params, state, actions, flags, seed=0, env_offset=0, common_
 _terrain_keep = None
 
 
-def set_terrain(vertices_world, heights_m):
+def set_terrain(vertices_world, heights_m, library=None):
     """lrl_oracle.c:lrlo_set_terrain — the terrain mesh the oracle's contacts and height scan use (params
-    terrain_mesh = 1): vertices [rows, cols, 3] in the world frame, height samples [rows, cols] in metres."""
+    terrain_mesh = 1): vertices [rows, cols, 3] in the world frame, height samples [rows, cols] in metres.  Each
+    build keeps its own mesh pointer (``library``: cpu_lib() for the float build), both read the same arrays."""
     global _terrain_keep
     v = np.ascontiguousarray(vertices_world, np.float32)
     h = np.ascontiguousarray(heights_m, np.float32)
     rows, cols = h.shape
     assert v.shape == (rows, cols, 3)
     _terrain_keep = (v, h)
-    lib().lrlo_set_terrain(v.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p), C.c_int(rows), C.c_int(cols))
+    (library or lib()).lrlo_set_terrain(v.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p), C.c_int(rows),
+                                        C.c_int(cols))
 
 
 def terrain_query(params, p, r):
@@ -150,15 +152,17 @@ def height_sample(params, root, k):
     return lib().lrlo_height_sample(C.byref(params), r.ctypes.data_as(C.c_void_p), C.c_int(k))
 
 
-def physics_substep(model, params, root, q, qd, tau, friction, restitution, payload, com):
+def physics_substep(model, params, root, q, qd, tau, friction, restitution, payload, com, library=None):
+    """lrl_oracle.c:lrlo_physics_substep — one cold-started sub-step of one env: (root, q, qd, contact forces [B, 3],
+    number of active ground contacts).  ``library``: cpu_lib() for the float build."""
     f = lambda a, n: np.ascontiguousarray(a, np.float32).reshape(n)
     root, q, qd, tau, com = f(root, 13), f(q, 12), f(qd, 12), f(tau, 12), f(com, 3)
     ro, qo, qdo = np.zeros(13, np.float32), np.zeros(12, np.float32), np.zeros(12, np.float32)
     co = np.zeros((model.num_bodies, 3), np.float32)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    n = lib().lrlo_physics_substep(C.byref(model), C.byref(params), p(root), p(q), p(qd), p(tau),
-                                   C.c_float(friction), C.c_float(restitution), C.c_float(payload), p(com), p(ro),
-                                   p(qo), p(qdo), p(co))
+    n = (library or lib()).lrlo_physics_substep(C.byref(model), C.byref(params), p(root), p(q), p(qd), p(tau),
+                                                C.c_float(friction), C.c_float(restitution), C.c_float(payload), p(com),
+                                                p(ro), p(qo), p(qdo), p(co))
     return ro, qo, qdo, co, n
 
 

@@ -227,18 +227,28 @@ def fk(model, root, com, q, qd, dtype=np.float64):
     rotations come from ``body_frames``; the velocities are the textbook recursion over the same chain: a joint adds
     qd times its world axis to the angular velocity, and a child origin at offset r from its parent's moves at
     v + w x r."""
-    root, com, q, qd = (np.asarray(a, dtype) for a in (root, com, q, qd))
-    R = quat_to_mat(root[3:7], dtype)
-    T = body_frames(model, root[0:3], R, q, dtype)
-    V, W = root[7:10], root[10:13]
-    v0 = V - np.cross(W, R @ com)
+    root = np.asarray(root, dtype)
+    return fk_mat(model, root[0:3], quat_to_mat(root[3:7], dtype), root[7:10], root[10:13], com, q, qd, dtype)
+
+
+def _cross(a, b):
+    """a x b of two 3-vectors, the products and differences np.cross takes, without its axis handling."""
+    return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]], a.dtype)
+
+
+def fk_mat(model, p, R, V, W, com, q, qd, dtype=np.float64):
+    """``fk`` from the base origin ``p``, the base rotation matrix ``R`` (base to world) and the world velocities V
+    (of the base's centre of mass) and W."""
+    p, R, V, W, com, q, qd = (np.asarray(a, dtype) for a in (p, R, V, W, com, q, qd))
+    T = body_frames(model, p, R, q, dtype)
+    v0 = V - _cross(W, R @ com)
     B = T.shape[0]
     pos, rot = T[:, :3, 3].copy(), T[:, :3, :3].copy()
     vel, ang = np.empty((B, 3), dtype), np.empty((B, 3), dtype)
     index = {(leg, link): b for b, (leg, link) in enumerate(zip(model["body_leg"], model["body_link"]))}
     done = {}
     for leg in range(4):
-        o, v, w = root[0:3], v0, W
+        o, v, w = p, v0, W
         Rp = R
         for j in range(3):
             Rj = Rp @ quat_to_mat(model["joint_quat"][leg][j], dtype) @ axis_angle_mat(
@@ -246,11 +256,11 @@ def fk(model, root, com, q, qd, dtype=np.float64):
             r = Rp @ np.asarray(model["joint_xyz"][leg][j], dtype)
             a = np.asarray(model["joint_axis"][leg][j], dtype)
             a = a / np.sqrt(np.sum(a * a, dtype=dtype))
-            v = v + np.cross(w, r)
+            v = v + _cross(w, r)
             w = w + qd[3 * leg + j] * (Rj @ a)
             o, Rp = o + r, Rj
             done[leg, j] = (v, w)
-        done[leg, 3] = (v + np.cross(w, Rp @ np.asarray(model["foot_xyz"][leg], dtype)), w)
+        done[leg, 3] = (v + _cross(w, Rp @ np.asarray(model["foot_xyz"][leg], dtype)), w)
     for (leg, link), b in index.items():
         vel[b], ang[b] = (v0, W) if leg < 0 else done[leg, link]
     return pos, rot, vel, ang

@@ -53,6 +53,31 @@ def make_rough(robot="go1", border_size=2.0, **over):
     return cfg, rob, M, P
 
 
+@functools.lru_cache(None)
+def robot_table(name, **over):
+    """(reference table in float64 of the float32 values the device gets, lrl_model, params) of "mc", "go1" or
+    "go1_random_joints" (Go1 with a real fixed rotation and a general axis at every joint): the FK keys of
+    aux_ref.fk and the mass tables of dyn_ref.robot.  ``over``: cfg overrides as in ``make``."""
+    from lrl import _abi
+    F32 = np.float32
+    _, rob, M, P = make("mc" if name == "mc" else "go1", **over)
+    keys = ("joint_xyz", "joint_quat", "joint_axis", "foot_xyz", "base_mass", "base_inertia", "link_mass", "link_com",
+            "link_inertia")
+    model = {k: np.asarray(rob[k], F32) for k in keys}
+    if name == "go1_random_joints":
+        rng = np.random.default_rng(11)
+        jq, ja = rng.normal(size=(4, 3, 4)), rng.normal(size=(4, 3, 3))
+        model["joint_quat"] = (jq / np.linalg.norm(jq, axis=-1, keepdims=True)).astype(F32)
+        model["joint_axis"] = (ja / np.linalg.norm(ja, axis=-1, keepdims=True)).astype(F32)
+        M2 = type(M).from_buffer_copy(M)
+        M2._base = M  # (keeps the hull table the copied pointer names alive)
+        _abi.fill(M2, joint_quat=model["joint_quat"].tolist(), joint_axis=model["joint_axis"].tolist())
+        M = M2
+    model = {k: v.astype(np.float64) for k, v in model.items()}
+    model["body_leg"], model["body_link"] = list(rob["body_leg"]), list(rob["body_link"])
+    return model, M, P
+
+
 ALL_TERMS = {"rewards.scales.energy": -1e-3, "rewards.scales.energy_expenditure": -2e-3, "rewards.scales.dof_vel": -1e-4,
              "rewards.scales.survival": 0.3, "rewards.scales.dof_vel_limits": -0.5, "rewards.scales.torque_limits": -0.02,
              "rewards.scales.stumble": -0.4, "rewards.scales.stand_still": -0.2,

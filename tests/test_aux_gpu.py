@@ -32,7 +32,7 @@ import pytest
 import torch
 
 import aux_ref as ar
-from helpers import DEV, dev, make, make_rough, mc_sim, npy, same, sim_of, stream, sync, vp
+from helpers import DEV, dev, make, make_rough, mc_sim, npy, robot_table, same, sim_of, stream, sync, vp
 from lrl import _abi
 
 pytestmark = pytest.mark.gpu
@@ -70,23 +70,9 @@ MODELS = ("mc", "go1", "go1_random_joints")
 FK_QUANTITIES = ("pos", "rot", "vel", "ang")
 
 
-@functools.lru_cache(None)
 def _table(name):
     """(reference table in float64 of the float32 values the device gets, lrl_model, params)."""
-    _, rob, M, P = make("mc" if name == "mc" else "go1")
-    model = {k: np.asarray(rob[k], F32) for k in ("joint_xyz", "joint_quat", "joint_axis", "foot_xyz")}
-    if name == "go1_random_joints":  # a real fixed rotation and a general axis at every joint
-        rng = np.random.default_rng(11)
-        jq, ja = rng.normal(size=(4, 3, 4)), rng.normal(size=(4, 3, 3))
-        model["joint_quat"] = (jq / np.linalg.norm(jq, axis=-1, keepdims=True)).astype(F32)
-        model["joint_axis"] = (ja / np.linalg.norm(ja, axis=-1, keepdims=True)).astype(F32)
-        M2 = type(M).from_buffer_copy(M)
-        M2._base = M  # (keeps the hull table the copied pointer names alive)
-        _abi.fill(M2, joint_quat=model["joint_quat"].tolist(), joint_axis=model["joint_axis"].tolist())
-        M = M2
-    model = {k: v.astype(np.float64) for k, v in model.items()}
-    model["body_leg"], model["body_link"] = list(rob["body_leg"]), list(rob["body_link"])
-    return model, M, P
+    return robot_table(name)
 
 
 @functools.lru_cache(None)

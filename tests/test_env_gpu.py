@@ -296,6 +296,14 @@ def test_physics_matches_oracle(robot, n, steps):
     _physics_vs_oracle(robot, n, steps)
 
 
+@pytest.mark.parametrize("decimation", [1, 6])
+@pytest.mark.parametrize("robot,n,steps", [("mc", 256, 3), ("go1", 37, 3)])
+def test_physics_matches_oracle_at_other_decimations(robot, n, steps, decimation):
+    """control.decimation is a run-time bound of the kernel's sub-step loop (every other physics test runs the
+    presets' 4): one and six sub-steps per env step against the oracle, same tolerances and exclusion cap."""
+    _physics_vs_oracle(robot, n, steps, extra={"control.decimation": decimation})
+
+
 @pytest.mark.parametrize("robot,steps", [("mc", 1), ("go1", 1), ("mc", 3), ("go1", 3)])
 def test_lying_robots_match_oracle(robot, steps):
     """The leg colliders' support tables in contact: 1,024 robots lying on their sides, so the ab/ad /
