@@ -5,6 +5,7 @@ env / PPO entry points raise instead of falling back to any CPU or eager impleme
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LRL_LIB overrides the library path (instrumented development builds); the default is the in-tree build
@@ -236,28 +237,73 @@ def _fill_array(arr, v):
             arr[i] = x
 
 
-_lib = None
-
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
-# the files and order of csrc/Makefile's SRC_HASH (SRCS then HDRS)
-_HASHED = ["lrl_env_dispatch.hip", "lrl_aux.hip", "lrl_gae.hip", "lrl_gemm.hip", "lrl_ppo.hip", "lrl_capi.cpp", "lrl_curriculum.cpp",
-           "lrl_curriculum_dev.hip", "lrl_env_flat.hip", "lrl_render.hip", "lrl_env_mesh_tgs.hip", "lrl_metrics.hip", "lrl_env_mesh.hip", "lrl_nav.hip", "lrl_depth.hip", "lrl_kparams.h", "lrl_gemm.h", "../../include/lrl.h", "../../include/lrl_philox.h",
-           "lrl_env_layout.h", "lrl_env_step.h", "lrl_launch.h", "lrl_raycast.h", "Makefile"]  # (the build flags too: a library built with other flags is stale)
+_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "lrl.h")
 
 
 def source_hash():
-    """sha256 (first 16 hex digits) of the sources liblrl.so must have been built from."""
+    """sha256 (first 16 hex digits) of the sources liblrl.so must have been built from: the files of csrc/Makefile's
+    SRCS then HDRS, the order of its SRC_HASH (the Makefile is one of them: other build flags make a stale library)."""
     import hashlib
+    with open(os.path.join(_CSRC, "Makefile")) as f:
+        mk = f.read()
     h = hashlib.sha256()
-    for name in _HASHED:
-        with open(os.path.join(_CSRC, name), "rb") as f:
-            h.update(f.read())
+    for var in ("SRCS", "HDRS"):
+        for name in re.search(rf"^{var} = (.*)$", mk, re.M).group(1).split():
+            with open(os.path.join(_CSRC, name), "rb") as f:
+                h.update(f.read())
     return h.hexdigest()[:16]
 
 
+# the structs of include/lrl.h this module mirrors: a pointer to one of them is POINTER(mirror) in a signature
+MIRRORS = {"lrl_model": LrlModel, "lrl_env_params": LrlEnvParams, "lrl_group_params": LrlGroupParams,
+           "lrl_tensor": LrlTensor, "lrl_metrics_view": LrlMetricsView, "lrl_rollout_store": LrlRolloutStore,
+           "lrl_ppo_net": LrlPpoNet, "lrl_ppo_batch": LrlPpoBatch, "lrl_ppo_hparams": LrlPpoHparams,
+           "lrl_dev_curriculum": LrlDevCurriculum, "lrl_nav_state": LrlNavState, "lrl_gemm_desc": LrlGemmDesc,
+           "lrl_camera": LrlCamera, "lrl_depth_camera": LrlDepthCamera}
+_SCALARS = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+            "float": C.c_float, "double": C.c_double}
+_RETURNS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "const char*": C.c_char_p}
+
+
+def signatures(header):
+    """{name: (restype, argtypes)} of every lrl_* prototype in the text of a header.  The header is the ABI: scalars
+    take their exact-width type, a pointer to a mirrored struct is POINTER(mirror), every other pointer (data of any
+    element type, streams, opaque handles, out-pointers) is c_void_p.  It reads what lrl.h uses and nothing more: a
+    declaration of another form, or a type outside these maps, raises and names the function."""
+    src = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    src = re.sub(r"^[ \t]*#.*$", "", src, flags=re.M).replace('extern "C" {', "")
+    out = {}
+    for m in re.finditer(r"\b(lrl_\w+)\s*\(", src):
+        name = m.group(1)
+        ret = re.sub(r"\s*\*\s*", "*", " ".join(re.split(r"[;{}]", src[:m.start()])[-1].split()))
+        tail = re.match(r"([^()]*)\)\s*;", src[m.end():])
+        if ret not in _RETURNS or tail is None:
+            raise RuntimeError(f"include/lrl.h: cannot read the declaration of {name} (returns '{ret}')")
+        args = []
+        params = [p.strip() for p in tail.group(1).split(",")]
+        for p in ([] if params == ["void"] else params):
+            words = [w for w in p.replace("*", " ").split() if w != "const"]  # the type, then the name if present
+            if "[" in p or not 1 <= len(words) <= 2:
+                raise RuntimeError(f"include/lrl.h: cannot read parameter '{p}' of {name}")
+            if p.count("*") == 1 and words[0] in MIRRORS:
+                args.append(C.POINTER(MIRRORS[words[0]]))
+            elif "*" in p:
+                args.append(C.c_void_p)
+            elif words[0] in _SCALARS:
+                args.append(_SCALARS[words[0]])
+            else:
+                raise RuntimeError(f"include/lrl.h: parameter '{p}' of {name} has a type outside the ABI's type map")
+        out[name] = (_RETURNS[ret], args)
+    return out
+
+
+_lib = None
+
+
 def lib():
-    """liblrl.so, loaded once.  Raises (no fallback) if it was not built, or was built from other sources than the
-    ones in this tree (a stale binary)."""
+    """liblrl.so, loaded once, every function with the restype and argtypes include/lrl.h declares.  Raises (no
+    fallback) if it was not built, or was built from other sources than the ones in this tree (a stale binary)."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -269,36 +315,10 @@ def lib():
         if built != want and not os.environ.get("LRL_LIB"):
             raise RuntimeError(f"{LIB_PATH} was built from other sources (hash {built}, tree {want}); "
                                "rebuild it: __graft_entry__.build()")
-        L.lrl_last_error.restype = C.c_char_p
-        for name in ["lrl_sim_create", "lrl_sim_destroy", "lrl_sim_tensor", "lrl_sim_step", "lrl_sim_reset_idx",
-                     "lrl_sim_set_root_state_indexed", "lrl_sim_set_dof_state_indexed", "lrl_sim_inject_uniforms",
-                     "lrl_sim_refresh_rigid_body_state", "lrl_sim_shift_history", "lrl_sim_randomize", "lrl_gae",
-                     "lrl_sim_randomize_envs", "lrl_sim_set_eval_group",
-                     "lrl_ppo_act", "lrl_abi_version", "lrl_device_count", "lrl_gae_partial", "lrl_adv_normalize",
-                     "lrl_sim_reset_idx_ex", "lrl_sim_observe_idx", "lrl_sim_set_step_counter", "lrl_ppo_forward_backward",
-                     "lrl_ppo_optimizer_step", "lrl_ppo_adaptation_forward_backward", "lrl_ppo_adaptation_step",
-                     "lrl_gemm_f32", "lrl_gemm_f32_ex", "lrl_gemm_f32_multi", "lrl_ppo_timing", "lrl_ppo_act_student", "lrl_sim_set_terrain",
-                     "lrl_sim_terrain_curriculum", "lrl_sim_inject_reset_uniforms", "lrl_sim_inject_push_uniforms", "lrl_sim_timing",
-                     "lrl_sim_self_contact_stats", "lrl_ppo_store_step", "lrl_curriculum_sample",
-                     "lrl_curriculum_update_weights", "lrl_rows_mean_zero", "lrl_sim_step_code",
-                     "lrl_sim_apply_commands", "lrl_sim_extras_snapshot", "lrl_sim_env_lists",
-                     "lrl_sim_terrain_curriculum_dev", "lrl_sim_reset_idx_dev", "lrl_sim_observe_idx_dev",
-                     "lrl_rows_mean_zero_dev", "lrl_sim_curriculum_resample_dev", "lrl_debug_gemm_paths",
-                     "lrl_debug_sim_garbage", "lrl_debug_sim_arena", "lrl_sim_render", "lrl_sim_record",
-                     "lrl_debug_sim_lds_bytes", "lrl_sim_metrics_enable", "lrl_sim_metrics_clear",
-                     "lrl_sim_metrics_tensors", "lrl_sim_metrics_reduce", "lrl_nav_begin_step",
-                     "lrl_nav_end_step", "lrl_sim_depth"]:
-            getattr(L, name).restype = C.c_int32
-        L.lrl_sim_depth.argtypes = [C.c_void_p, C.POINTER(LrlDepthCamera), C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                    C.c_void_p, C.c_void_p]
-        L.lrl_nav_begin_step.argtypes = [C.c_void_p, C.POINTER(LrlNavState), C.c_void_p, C.c_void_p]
-        L.lrl_nav_end_step.argtypes = [C.c_void_p, C.POINTER(LrlNavState), C.c_uint32, C.c_int32, C.c_float, C.c_float,
-                                       C.c_float, C.c_float, C.c_void_p]
-        L.lrl_np_sum_f64.restype = C.c_double
-        L.lrl_np_sum_f64.argtypes = [C.c_void_p, C.c_int64]
-        L.lrl_ppo_workspace_bytes.restype = C.c_int64
-        L.lrl_ppo_act_workspace_bytes.restype = C.c_int64
-        L.lrl_ppo_act_student_workspace_bytes.restype = C.c_int64
+        with open(_HEADER) as f:
+            for name, (restype, argtypes) in signatures(f.read()).items():
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 

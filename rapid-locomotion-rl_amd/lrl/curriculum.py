@@ -6,7 +6,6 @@ a 3-D grid of command bins (lin_vel_x, lin_vel_y, ang_vel_yaw) with sampling wei
 bit for bit for the same seed.  This is bookkeeping on a few thousand bins once per resampling
 interval; it stays on the host like the reference.
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -100,14 +99,13 @@ class GridCurriculum:
             if not hasattr(self, "_grid_c"):  # (persistent arrays: their addresses are taken once)
                 self._grid_c = np.ascontiguousarray(self.grid, dtype=np.float64)
                 self._half_c = np.ascontiguousarray(np.array(list(self.bin_sizes.values()), np.float64) / 2)
-                self._ptrs = tuple(C.c_void_p(a.ctypes.data) for a in (self._mt_key, self._mt_pos, self._grid_c,
-                                                                       self._half_c))
+                self._ptrs = tuple(a.ctypes.data for a in (self._mt_key, self._mt_pos, self._grid_c, self._half_c))
             cmds = np.empty((batch_size, 3), np.float64)
             inds = np.empty(batch_size, np.int64)
             k, ps, g, h = self._ptrs
             L = _abi.lib()
-            rc = L.lrl_curriculum_sample(k, ps, C.c_void_p(w.ctypes.data), self._l, g, h, batch_size,
-                                         C.c_void_p(cmds.ctypes.data), C.c_void_p(inds.ctypes.data))
+            rc = L.lrl_curriculum_sample(k, ps, w.ctypes.data, self._l, g, h, batch_size, cmds.ctypes.data,
+                                         inds.ctypes.data)
             if rc != 0:
                 raise ValueError(L.lrl_last_error().decode())
             return cmds, inds
@@ -151,13 +149,12 @@ class RewardThresholdCurriculum(GridCurriculum):
             from . import _abi
             if not hasattr(self, "_axes_c"):
                 self._axes_c = np.ascontiguousarray(np.concatenate([self.cfg[k] for k in self.keys]), np.float64)
-                self._axes_p = C.c_void_p(self._axes_c.ctypes.data)
+                self._axes_p = self._axes_c.ctypes.data
                 self._axes_n = tuple(self.ls[k] for k in self.keys)
             cen = np.ascontiguousarray(centres, dtype=np.int64)
             nx, ny, nz = self._axes_n
             _abi.check(_abi.lib().lrl_curriculum_update_weights(
-                C.c_void_p(self.weights.ctypes.data), self._axes_p, nx, ny, nz, C.c_void_p(cen.ctypes.data), len(cen),
-                C.c_double(float(local_range))))
+                self.weights.ctypes.data, self._axes_p, nx, ny, nz, cen.ctypes.data, len(cen), float(local_range)))
             return
         self.weights[bin_inds[ok]] = np.clip(self.weights[bin_inds[ok]] + 0.2, 0, 1)
         if len(centres) == 0:

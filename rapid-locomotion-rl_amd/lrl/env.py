@@ -283,8 +283,7 @@ class LeggedRobotEnv:
         self._sim = C.c_void_p()
         torch.cuda.set_device(self.device)
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        _abi.check(L.lrl_sim_create(C.byref(self._M), C.byref(self._P), C.c_int32(self.num_envs),
-                                    C.c_int64(env_offset), C.c_uint64(self.seed), C.c_int32(dev_index),
+        _abi.check(L.lrl_sim_create(C.byref(self._M), C.byref(self._P), self.num_envs, env_offset, self.seed, dev_index,
                                     C.byref(self._sim)))
         self._dev_index = dev_index
         if self._G is not None:
@@ -298,8 +297,7 @@ class LeggedRobotEnv:
                                                         cfg.terrain.vertical_scale, None)
             vtx = np.ascontiguousarray(vtx, np.float32)
             hs = np.ascontiguousarray(t.heightsamples, np.int16)
-            _abi.check(L.lrl_sim_set_terrain(self._sim, vtx.ctypes.data_as(C.c_void_p), hs.ctypes.data_as(C.c_void_p),
-                                             C.c_int32(hs.shape[0]), C.c_int32(hs.shape[1])))
+            _abi.check(L.lrl_sim_set_terrain(self._sim, vtx.ctypes.data, hs.ctypes.data, hs.shape[0], hs.shape[1]))
         self.height_samples = (torch.tensor(self.terrain.heightsamples).to(self.device)
                                if self.terrain is not None else None)
         T = self._tensor
@@ -398,11 +396,11 @@ class LeggedRobotEnv:
             which = (int(dr.randomize_base_mass) | (int(dr.randomize_com_displacement) << 1) |
                      (int(dr.randomize_friction) << 2) | (int(dr.randomize_restitution) << 3))
             ranges = (arr(dr.friction_range), arr(dr.restitution_range), arr(dr.added_mass_range),
-                      arr(dr.com_displacement_range), C.c_uint32(which), self._stream())
+                      arr(dr.com_displacement_range), which, self._stream())
             if first is None:
                 _abi.check(L.lrl_sim_randomize(self._sim, *ranges))
             else:
-                _abi.check(L.lrl_sim_randomize_envs(self._sim, C.c_int32(first), C.c_int32(count), *ranges))
+                _abi.check(L.lrl_sim_randomize_envs(self._sim, first, count, *ranges))
         if eval_cfg is None:
             rigid_body_draw(cfg.domain_rand)
         else:  # each group with its own cfg's switches and ranges (_call_train_eval, :1231); keys are global env ids
@@ -526,7 +524,7 @@ class LeggedRobotEnv:
     # -------------------------------------------------------------------------------- plumbing
     def _tensor(self, tid):
         d = _abi.LrlTensor()
-        _abi.check(self._L.lrl_sim_tensor(self._sim, C.c_int32(tid), C.byref(d)))
+        _abi.check(self._L.lrl_sim_tensor(self._sim, tid, C.byref(d)))
         return _dlpack.wrap(d, self._dev_index)
 
     def _stream(self):
@@ -718,10 +716,9 @@ class LeggedRobotEnv:
         cd = up[0 if _ids32 is not None else 1]
         bins = up[-1] if _bins_to is not None else None
         _abi.check(self._L.lrl_sim_apply_commands(
-            self._sim, C.c_void_p(ids32.data_ptr()), C.c_int32(len(ids_np)), C.c_void_p(cd.data_ptr()),
-            C.c_void_p(bins.data_ptr() if bins is not None else 0),
-            C.c_void_p(_bins_to.data_ptr() if _bins_to is not None else 0),
-            C.c_int32(len(_bins_to) if _bins_to is not None else 0), self._stream()))
+            self._sim, ids32.data_ptr(), len(ids_np), cd.data_ptr(), bins.data_ptr() if bins is not None else None,
+            _bins_to.data_ptr() if _bins_to is not None else None, len(_bins_to) if _bins_to is not None else 0,
+            self._stream()))
         # (the kernel's writes do not move the tensors' version counters: the step's host copy of the tracking sums,
         # zeroed above for these ids, stays valid)
 
@@ -754,7 +751,7 @@ class LeggedRobotEnv:
         self._sums_host = None  # the kernel below changes the command sums
         if tm is not None:
             tm.mark("pre_resample")
-        _abi.check(self._L.lrl_sim_step(self._sim, C.c_void_p(actions.data_ptr()), C.c_uint32(flags), self._stream()))
+        _abi.check(self._L.lrl_sim_step(self._sim, actions.data_ptr(), flags, self._stream()))
         self.common_step_counter += 1
         if not self.legacy_fork:  # reset_idx of the terminated / timed-out envs, then their observations
             # one device->host copy per step: bit 0 = reset now, bit 1 = due for resampling next step (episode
@@ -769,9 +766,8 @@ class LeggedRobotEnv:
                 self._code_host = torch.empty(3 * self.num_envs, dtype=torch.float32, pin_memory=True).numpy()
                 self._rid32 = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
             # (the reset ids are compacted on the device in the same call: no host -> device upload of them)
-            _abi.check(self._L.lrl_sim_step_code(self._sim, C.c_int32(interval), C.c_int32(tr[0]), C.c_int32(tr[1]),
-                                                 C.c_void_p(self._code_host.ctypes.data),
-                                                 C.c_void_p(self._rid32.data_ptr()), self._stream()))
+            _abi.check(self._L.lrl_sim_step_code(self._sim, interval, tr[0], tr[1], self._code_host.ctypes.data,
+                                                 self._rid32.data_ptr(), self._stream()))
             pack = self._code_host.reshape(3, self.num_envs)
             code = pack[0].astype(np.uint8)
             if self._track_rows is not None:
@@ -786,8 +782,7 @@ class LeggedRobotEnv:
                 if tm is not None:
                     tm.mark("ids_h2d")
                 self.reset_idx(ids32, ids_np, _ids32=ids32)
-                _abi.check(self._L.lrl_sim_observe_idx(self._sim, C.c_void_p(ids32.data_ptr()), C.c_int32(len(ids32)),
-                                                       C.c_uint32(flags), self._stream()))
+                _abi.check(self._L.lrl_sim_observe_idx(self._sim, ids32.data_ptr(), len(ids32), flags, self._stream()))
             self._due_next = (eplen._version, due_np)
             if tm is not None:
                 tm.mark("reset_idx_observe")
@@ -827,7 +822,7 @@ class LeggedRobotEnv:
                 ex.set_lazy(key, lambda fn=fn: fn().cpu().numpy().copy())
             return
         snap = torch.empty(self._EXTRAS_ROWS, n, device=self.device)
-        _abi.check(self._L.lrl_sim_extras_snapshot(self._sim, C.c_void_p(snap.data_ptr()), self._stream()))
+        _abi.check(self._L.lrl_sim_extras_snapshot(self._sim, snap.data_ptr(), self._stream()))
         nf = len(self.feet_indices)
 
         def read(key):
@@ -857,37 +852,34 @@ class LeggedRobotEnv:
             self._dev_upload()
         d = self._dcur
         n = self.num_envs
-        vp = lambda t: C.c_void_p(t.data_ptr())
         interval = self._resample_interval()
         # (max_episode_length is a float, np.ceil's; an integral value either way, as the divisor of the tracking sums)
         ep_len = int(min(self.cfg.env.max_episode_length, interval))
-        lin_thr = self.cfg.commands.forward_curriculum_threshold * self.reward_scales["tracking_lin_vel"]
-        ang_thr = self.cfg.commands.yaw_curriculum_threshold * self.reward_scales["tracking_ang_vel"]
+        lin_thr = float(self.cfg.commands.forward_curriculum_threshold * self.reward_scales["tracking_lin_vel"])
+        ang_thr = float(self.cfg.commands.yaw_curriculum_threshold * self.reward_scales["tracking_ang_vel"])
         due, rst = d["ids"]
         cnt = d["cnt"]
-        due_n, rst_n = C.c_void_p(cnt.data_ptr()), C.c_void_p(cnt.data_ptr() + 4)
+        due_n, rst_n = cnt.data_ptr(), cnt.data_ptr() + 4
         r0, r1 = self._track_rows
 
         def resample(ids, count, log_area):
-            _abi.check(L.lrl_sim_curriculum_resample_dev(sim, C.byref(d["desc"]), vp(ids), C.c_int32(n), count,
-                                                         C.c_int32(ep_len), C.c_int32(r0), C.c_int32(r1),
-                                                         C.c_double(lin_thr), C.c_double(ang_thr), C.c_double(0.5),
-                                                         C.c_int32(1), C.c_int32(log_area), st))
+            _abi.check(L.lrl_sim_curriculum_resample_dev(sim, d["desc"], ids.data_ptr(), n, count, ep_len, r0, r1,
+                                                         lin_thr, ang_thr, 0.5, 1, log_area, st))
         # _post_physics_step_callback's resampling of the envs whose episode reaches a multiple of resampling_time
-        _abi.check(L.lrl_sim_env_lists(sim, C.c_int32(1), C.c_int32(interval), vp(due), due_n, st))
+        _abi.check(L.lrl_sim_env_lists(sim, 1, interval, due.data_ptr(), due_n, st))
         resample(due, due_n, 0)
-        _abi.check(L.lrl_sim_step(sim, vp(actions), C.c_uint32(flags), st))
+        _abi.check(L.lrl_sim_step(sim, actions.data_ptr(), flags, st))
         self.common_step_counter += 1
         # reset_idx of the terminated / timed-out envs (legged_robot.py:227-290), then their observations
-        _abi.check(L.lrl_sim_env_lists(sim, C.c_int32(0), C.c_int32(interval), vp(rst), rst_n, st))
+        _abi.check(L.lrl_sim_env_lists(sim, 0, interval, rst.data_ptr(), rst_n, st))
         cfg = self.cfg
         if self.custom_origins and cfg.terrain.curriculum:
             t = cfg.terrain
             to = t.terrain_origins
             _abi.check(L.lrl_sim_terrain_curriculum_dev(
-                sim, vp(rst), C.c_int32(n), rst_n, vp(self.terrain_levels), vp(self.terrain_types), vp(to),
-                C.c_int32(to.shape[0]), C.c_int32(to.shape[1]), C.c_float(t.env_length / 2),
-                C.c_float(cfg.env.episode_length_s), C.c_int32(t.max_terrain_level), st))
+                sim, rst.data_ptr(), n, rst_n, self.terrain_levels.data_ptr(), self.terrain_types.data_ptr(),
+                to.data_ptr(), to.shape[0], to.shape[1], float(t.env_length / 2), float(cfg.env.episode_length_s),
+                t.max_terrain_level, st))
         c = cfg.commands
         if (c.command_curriculum or c.yaw_command_curriculum) and self.common_step_counter % cfg.env.max_episode_length == 0:
             k = int(cnt[1].item())  # (the uniform command-range curriculum's step: once per episode length, host sync)
@@ -916,15 +908,14 @@ class LeggedRobotEnv:
         es = self._episode_sums
         R = es.shape[0]
         pub = torch.empty(R + 1, device=self.device)  # [means of the last reset batch | terrain level]
-        _abi.check(L.lrl_rows_mean_zero_dev(vp(es), C.c_int64(es.stride(0)), C.c_int32(R), vp(rst), C.c_int32(n), rst_n,
-                                            vp(pub), vp(d["means"]), C.c_int32(1), st))
+        _abi.check(L.lrl_rows_mean_zero_dev(es.data_ptr(), es.stride(0), R, rst.data_ptr(), n, rst_n, pub.data_ptr(),
+                                            d["means"].data_ptr(), 1, st))
         d["means"] = pub[:R]
         t = cfg.terrain
-        _abi.check(L.lrl_sim_reset_idx_dev(sim, vp(rst), C.c_int32(n), rst_n, C.c_int32(self._root_mode()),
-                                           C.c_float(float(t.x_init_range)),
-                                           C.c_float(float(t.y_init_range) - float(t.x_init_range)),
-                                           C.c_float(float(t.x_init_offset)), C.c_float(float(t.y_init_offset)), st))
-        _abi.check(L.lrl_sim_observe_idx_dev(sim, vp(rst), C.c_int32(n), rst_n, C.c_uint32(flags), st))
+        _abi.check(L.lrl_sim_reset_idx_dev(sim, rst.data_ptr(), n, rst_n, self._root_mode(), float(t.x_init_range),
+                                           float(t.y_init_range) - float(t.x_init_range), float(t.x_init_offset),
+                                           float(t.y_init_offset), st))
+        _abi.check(L.lrl_sim_observe_idx_dev(sim, rst.data_ptr(), n, rst_n, flags, st))
         self._due_next = None
         self._sums_host = None
         ep = d["ep"] = {"rew_" + k: m for k, m in zip(self.episode_sums, pub[:R].unbind(0))}
@@ -999,7 +990,7 @@ class LeggedRobotEnv:
         env_step_kernel launch of lrl_sim_step on its own stream (lrl_sim_timing; the history-shift launch before it
         is outside).  start=True begins recording; start=False stops and returns (mean ms, total ms, launches)."""
         ms, n = C.c_double(0.0), C.c_int64(0)
-        _abi.check(self._L.lrl_sim_timing(self._sim, C.c_int32(1 if start else 0), C.byref(ms), C.byref(n)))
+        _abi.check(self._L.lrl_sim_timing(self._sim, 1 if start else 0, C.byref(ms), C.byref(n)))
         if start:
             return None
         return (ms.value / n.value if n.value else float("nan")), ms.value, n.value
@@ -1008,7 +999,7 @@ class LeggedRobotEnv:
         """lrl_sim_self_contact_stats: start=True zeroes the device counters and starts counting; start=False stops and
         returns {env_substeps_in_self_contact, self_pairs_in_contact, env_substeps_over_cap, self_pairs_dropped}."""
         out = (C.c_uint64 * 4)()
-        _abi.check(self._L.lrl_sim_self_contact_stats(self._sim, C.c_int32(1 if start else 0), out))
+        _abi.check(self._L.lrl_sim_self_contact_stats(self._sim, 1 if start else 0, out))
         if start:
             return None
         return dict(zip(("env_substeps_in_self_contact", "self_pairs_in_contact", "env_substeps_over_cap",
@@ -1053,9 +1044,8 @@ class LeggedRobotEnv:
         rgba = torch.empty(h, w, 4, dtype=torch.uint8, device=self.device)
         dep = torch.empty(h, w, dtype=torch.float32, device=self.device) if depth else None
         idt = torch.empty(h, w, dtype=torch.int32, device=self.device) if ids else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        _abi.check(self._L.lrl_sim_render(self._sim, C.c_int32(env_id), C.byref(cam), ptr(rgba), ptr(dep), ptr(idt),
-                                          self._stream()))
+        _abi.check(self._L.lrl_sim_render(self._sim, env_id, cam, rgba.data_ptr(), dep.data_ptr() if depth else None,
+                                          idt.data_ptr() if ids else None, self._stream()))
         return rgba, dep, idt
 
     def render(self, mode="rgb_array"):
@@ -1066,8 +1056,8 @@ class LeggedRobotEnv:
 
     def _depth_launch(self, only_reset, ids=None):
         _abi.check(self._L.lrl_sim_depth(self._sim, C.byref(self._depth_cam), 0, self.num_envs, int(only_reset),
-                                         C.c_void_p(self.depth_images.data_ptr()),
-                                         C.c_void_p(ids.data_ptr()) if ids is not None else None, self._stream()))
+                                         self.depth_images.data_ptr(), ids.data_ptr() if ids is not None else None,
+                                         self._stream()))
 
     def _depth_tick(self):
         """The depth camera's part of step(), after the step's resets and re-observation: every update_interval-th
@@ -1139,10 +1129,8 @@ class LeggedRobotEnv:
             if es.stride(1) == 1 and es.is_cuda:  # means and zeroing in one launch (lrl_rows_mean_zero)
                 tr32 = _ids32 if _ids32 is not None else tr.to(torch.int32).contiguous()
                 means = torch.empty(es.shape[0], device=self.device)
-                _abi.check(self._L.lrl_rows_mean_zero(C.c_void_p(es.data_ptr()), C.c_int64(es.stride(0)),
-                                                      C.c_int32(es.shape[0]), C.c_void_p(tr32.data_ptr()),
-                                                      C.c_int32(len(tr32)), C.c_void_p(means.data_ptr()), C.c_int32(1),
-                                                      self._stream()))
+                _abi.check(self._L.lrl_rows_mean_zero(es.data_ptr(), es.stride(0), es.shape[0], tr32.data_ptr(),
+                                                      len(tr32), means.data_ptr(), 1, self._stream()))
             else:
                 means = es[:, tr].mean(dim=1)
                 es[:, tr] = 0.0
@@ -1211,14 +1199,13 @@ class LeggedRobotEnv:
             if inj is not None:
                 rows = inj if len(ids) == len(env_ids) else inj[torch.isin(env_ids, ids)]
                 rows = rows.to(self.device, torch.float32).contiguous()
-                _abi.check(self._L.lrl_sim_inject_reset_uniforms(self._sim, C.c_void_p(rows.data_ptr())))
+                _abi.check(self._L.lrl_sim_inject_reset_uniforms(self._sim, rows.data_ptr()))
                 flags = _abi.STEP_INJECT_UNIFORM
             t = c.terrain
             _abi.check(self._L.lrl_sim_reset_idx_ex(
-                self._sim, C.c_void_p(ids32.data_ptr()), C.c_int32(len(ids32)), C.c_int32(mode),
-                C.c_float(float(t.x_init_range)), C.c_float(float(t.y_init_range) - float(t.x_init_range)),
-                C.c_float(float(t.x_init_offset)),
-                C.c_float(float(t.y_init_offset)), C.c_uint32(flags), self._stream()))
+                self._sim, ids32.data_ptr(), len(ids32), mode, float(t.x_init_range),
+                float(t.y_init_range) - float(t.x_init_range), float(t.x_init_offset), float(t.y_init_offset), flags,
+                self._stream()))
             if inj is not None:
                 torch.cuda.current_stream(self.device).synchronize()  # rows must outlive the launch
 
@@ -1247,11 +1234,9 @@ class LeggedRobotEnv:
             ids32 = _ids32 if _ids32 is not None else env_ids.to(torch.int32).contiguous()
             to = t.terrain_origins
             _abi.check(self._L.lrl_sim_terrain_curriculum(
-                self._sim, C.c_void_p(ids32.data_ptr()), C.c_int32(len(ids32)), C.c_void_p(self.terrain_levels.data_ptr()),
-                C.c_void_p(self.terrain_types.data_ptr()), C.c_void_p(rnd.data_ptr() if rnd is not None else 0),
-                C.c_void_p(to.data_ptr()),
-                C.c_int32(to.shape[0]), C.c_int32(to.shape[1]), C.c_float(t.env_length / 2),
-                C.c_float(cfg.env.episode_length_s), C.c_int32(t.max_terrain_level), self._stream()))
+                self._sim, ids32.data_ptr(), len(ids32), self.terrain_levels.data_ptr(), self.terrain_types.data_ptr(),
+                rnd.data_ptr() if rnd is not None else None, to.data_ptr(), to.shape[0], to.shape[1],
+                float(t.env_length / 2), float(cfg.env.episode_length_s), t.max_terrain_level, self._stream()))
             return
         distance = torch.norm(self.root_states[env_ids, :2] - self.env_origins[env_ids, :2], dim=1)
         move_up = distance > t.env_length / 2
@@ -1316,16 +1301,14 @@ class LeggedRobotEnv:
     def set_actor_root_state_tensor_indexed(self, root_states, env_ids):
         ids = torch.as_tensor(env_ids, device=self.device).to(torch.int32).contiguous()
         src = root_states.contiguous()
-        _abi.check(self._L.lrl_sim_set_root_state_indexed(self._sim, C.c_void_p(src.data_ptr()),
-                                                          C.c_void_p(ids.data_ptr()), C.c_int32(len(ids)),
+        _abi.check(self._L.lrl_sim_set_root_state_indexed(self._sim, src.data_ptr(), ids.data_ptr(), len(ids),
                                                           self._stream()))
 
     def set_dof_state_tensor_indexed(self, dof_pos, dof_vel, env_ids):
         ids = torch.as_tensor(env_ids, device=self.device).to(torch.int32).contiguous()
         p, v = dof_pos.contiguous(), dof_vel.contiguous()
-        _abi.check(self._L.lrl_sim_set_dof_state_indexed(self._sim, C.c_void_p(p.data_ptr()), C.c_void_p(v.data_ptr()),
-                                                         C.c_void_p(ids.data_ptr()), C.c_int32(len(ids)),
-                                                         self._stream()))
+        _abi.check(self._L.lrl_sim_set_dof_state_indexed(self._sim, p.data_ptr(), v.data_ptr(), ids.data_ptr(),
+                                                         len(ids), self._stream()))
 
     def shift_history(self):
         _abi.check(self._L.lrl_sim_shift_history(self._sim, self._stream()))
@@ -1350,9 +1333,8 @@ class LeggedRobotEnv:
     def _record_frame(self, key):
         r = self._rec.get(key)
         if r is not None:
-            _abi.check(self._L.lrl_sim_record(self._sim, C.c_int32(r["env"]), C.byref(r["camera"]),
-                                              C.c_void_p(r["ring"].data_ptr()), C.c_int32(r["capacity"]),
-                                              C.c_void_p(r["state"].data_ptr()), self._stream()))
+            _abi.check(self._L.lrl_sim_record(self._sim, r["env"], r["camera"], r["ring"].data_ptr(), r["capacity"],
+                                              r["state"].data_ptr(), self._stream()))
 
     def _complete_frames(self, key):
         """The finished video as a list of numpy frames, [] while it is not complete; the second value tells that the

@@ -39,13 +39,13 @@ class EvalMetrics:
     # ---- switches
     def enable(self):
         """Launch the metrics kernel in every later step (the first call allocates the tables, totals cleared)."""
-        _abi.check(self._L.lrl_sim_metrics_enable(self.env._sim, C.c_int32(1)))
+        _abi.check(self._L.lrl_sim_metrics_enable(self.env._sim, 1))
         self.enabled = True
         self._tables()
         return self
 
     def disable(self):
-        _abi.check(self._L.lrl_sim_metrics_enable(self.env._sim, C.c_int32(0)))
+        _abi.check(self._L.lrl_sim_metrics_enable(self.env._sim, 0))
         self.enabled = False
 
     def clear(self):
@@ -125,8 +125,8 @@ class EvalMetrics:
         first, count = self.group_range(group)
         if self._out is None:
             self._out = torch.empty(_abi.METRICS_REDUCE_DOUBLES, dtype=torch.float64, device=self.env.device)
-        _abi.check(self._L.lrl_sim_metrics_reduce(self.env._sim, C.c_int32(first), C.c_int32(count),
-                                                  C.c_void_p(self._out.data_ptr()), self.env._stream()))
+        _abi.check(self._L.lrl_sim_metrics_reduce(self.env._sim, first, count, self._out.data_ptr(),
+                                                  self.env._stream()))
         return self._out.cpu()
 
     def summary(self, group="all"):

@@ -357,26 +357,25 @@ class HighLevelControlWrapper:
         order = ("train/episode", "eval/episode", "ll")
         v.means_train, v.means_eval, v.means_ll = (slots[k].data_ptr() for k in order)
         v.prev_train, v.prev_eval, v.prev_ll = (prev[k].data_ptr() for k in order)
-        _abi.check(L.lrl_nav_begin_step(e._sim, C.byref(v), C.c_void_p(actions.data_ptr()), e._stream()))
+        _abi.check(L.lrl_nav_begin_step(e._sim, C.byref(v), actions.data_ptr(), e._stream()))
         with torch.no_grad():
             ll_actions = self.low_level_policy(self.ll_obs)
         self.ll_obs, self.ll_rew, self.ll_dones, self.ll_info = self.ll_env.step(ll_actions)
         t = e.cfg.terrain
-        reset_args = (C.c_int32(e._root_mode()), C.c_float(float(t.x_init_range)),
-                      C.c_float(float(t.y_init_range) - float(t.x_init_range)), C.c_float(float(t.x_init_offset)),
-                      C.c_float(float(t.y_init_offset)), e._stream())
+        reset_args = (e._root_mode(), float(t.x_init_range), float(t.y_init_range) - float(t.x_init_range),
+                      float(t.x_init_offset), float(t.y_init_offset), e._stream())
         c = e.cfg.commands
         if (c.command_curriculum or c.yaw_command_curriculum) and \
                 e.common_step_counter % e.cfg.env.max_episode_length == 0:
             # the uniform command-range curriculum's step (once per episode length): it reads the batch's tracking sums
             # on the host before they are zeroed, so the ids are made first and their count read (a stream sync)
-            _abi.check(L.lrl_nav_end_step(e._sim, C.byref(v), C.c_uint32(_abi.NAV_ONLY_FLAGS), *reset_args))
+            _abi.check(L.lrl_nav_end_step(e._sim, C.byref(v), _abi.NAV_ONLY_FLAGS, *reset_args))
             k = int(self._cnt.item())
             if k:
                 e.update_command_curriculum(self._ids[:k].long(), e.cfg)
-            _abi.check(L.lrl_nav_end_step(e._sim, C.byref(v), C.c_uint32(_abi.NAV_ONLY_RESET), *reset_args))
+            _abi.check(L.lrl_nav_end_step(e._sim, C.byref(v), _abi.NAV_ONLY_RESET, *reset_args))
         else:
-            _abi.check(L.lrl_nav_end_step(e._sim, C.byref(v), C.c_uint32(0), *reset_args))
+            _abi.check(L.lrl_nav_end_step(e._sim, C.byref(v), 0, *reset_args))
         self._prev = slots
         keys = ["train/episode"] + (["eval/episode"] if self.num_envs > self.num_train_envs else [])
         for key in keys:

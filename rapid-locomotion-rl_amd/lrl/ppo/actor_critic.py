@@ -192,17 +192,15 @@ class ActorCritic(nn.Module):
         net = self.flatten_parameters()
         ws = getattr(self, "_student_ws", None)
         if ws is None or ws[0] != n or ws[1].device != dev:
-            nbytes = _abi.lib().lrl_ppo_act_student_workspace_bytes(C.byref(net), C.c_int32(n))
+            nbytes = _abi.lib().lrl_ppo_act_student_workspace_bytes(C.byref(net), n)
             if nbytes < 0:
                 raise RuntimeError("lrl_ppo_act_student_workspace_bytes rejected the network")
             ws = self._student_ws = (n, torch.empty(nbytes, dtype=torch.uint8, device=dev))
         mean = torch.empty(n, self.num_actions, device=dev)
         latent = torch.empty(n, net.latent, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        stream = _abi.stream_of(dev)
-        _abi.check(_abi.lib().lrl_ppo_act_student(C.byref(net), ptr(self._flat), ptr(obs), ptr(hist),
-                                                  C.c_int32(hist.stride(0)), C.c_int32(n), ptr(mean), ptr(latent),
-                                                  ptr(ws[1]), stream))
+        _abi.check(_abi.lib().lrl_ppo_act_student(net, self._flat.data_ptr(), obs.data_ptr(), hist.data_ptr(),
+                                                  hist.stride(0), n, mean.data_ptr(), latent.data_ptr(),
+                                                  ws[1].data_ptr(), _abi.stream_of(dev)))
         return mean, latent
 
     def act_fused(self, obs, priv, hist=None, eps=None, seed=0, counter=0, store=None, store_row=0, row_offset=0):
@@ -217,7 +215,7 @@ class ActorCritic(nn.Module):
         net = self.flatten_parameters()
         ws = getattr(self, "_act_ws", None)
         if ws is None or ws[0] != n or ws[1].device != dev:
-            nbytes = _abi.lib().lrl_ppo_act_workspace_bytes(C.byref(net), C.c_int32(n))
+            nbytes = _abi.lib().lrl_ppo_act_workspace_bytes(C.byref(net), n)
             if nbytes < 0:
                 raise RuntimeError("lrl_ppo_act_workspace_bytes rejected the network")
             ws = self._act_ws = (n, torch.empty(nbytes, dtype=torch.uint8, device=dev))
@@ -225,11 +223,8 @@ class ActorCritic(nn.Module):
         mu = torch.empty(n, self.num_actions, device=dev)
         values = torch.empty(n, 1, device=dev)
         logp = torch.empty(n, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        st = C.byref(store) if store is not None else None
-        stream = _abi.stream_of(dev)
-        _abi.check(_abi.lib().lrl_ppo_act(C.byref(net), ptr(self._flat), ptr(obs), ptr(priv), ptr(hist), C.c_int32(n),
-                                          ptr(eps), C.c_uint64(seed), C.c_uint64(counter), C.c_int64(row_offset),
-                                          ptr(actions), ptr(mu),
-                                          ptr(values), ptr(logp), st, C.c_int32(store_row), ptr(ws[1]), stream))
+        priv_p, hist_p, eps_p = (t.data_ptr() if t is not None else None for t in (priv, hist, eps))
+        _abi.check(_abi.lib().lrl_ppo_act(net, self._flat.data_ptr(), obs.data_ptr(), priv_p, hist_p, n, eps_p, seed,
+                                          counter, row_offset, actions.data_ptr(), mu.data_ptr(), values.data_ptr(),
+                                          logp.data_ptr(), store, store_row, ws[1].data_ptr(), _abi.stream_of(dev)))
         return actions, mu, values, logp

@@ -173,11 +173,11 @@ class PPO:
         if s.step >= s.num_transitions_per_env:
             raise AssertionError("Rollout buffer overflow")
         i = s.step
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
-        stream = _abi.stream_of(rewards.device)
-        _abi.check(_abi.lib().lrl_ppo_store_step(p(rewards), p(dones), p(bins), p(t.values if tout is not None else None),
-                                                 p(tout), C.c_float(self.args.gamma), C.c_int32(n), p(s.rewards[i]),
-                                                 p(s.dones[i]), p(s.env_bins[i]), stream))
+        values, tout = (t.values.data_ptr(), tout.data_ptr()) if tout is not None else (None, None)
+        _abi.check(_abi.lib().lrl_ppo_store_step(rewards.data_ptr(), dones.data_ptr(), bins.data_ptr(), values, tout,
+                                                 float(self.args.gamma), n, s.rewards[i].data_ptr(),
+                                                 s.dones[i].data_ptr(), s.env_bins[i].data_ptr(),
+                                                 _abi.stream_of(rewards.device)))
         s.step += 1
         return True
 
@@ -227,7 +227,7 @@ class PPO:
             st["hp"] = hp
             self._native = st
         if st["ws_batch"] != batch:
-            nbytes = _abi.lib().lrl_ppo_workspace_bytes(C.byref(net), C.c_int32(batch))
+            nbytes = _abi.lib().lrl_ppo_workspace_bytes(C.byref(net), batch)
             if nbytes < 0:
                 raise RuntimeError("lrl_ppo_workspace_bytes rejected the network")
             st["ws"] = torch.empty(nbytes, dtype=torch.uint8, device=ac._flat.device)
@@ -263,7 +263,6 @@ class PPO:
         world = _world()
         coll = _collective()
         L = _abi.lib()
-        ptr = lambda t: C.c_void_p(t.data_ptr())
         stream = _abi.stream_of(st["grads"].device)
         indices = torch.randperm(nmb * mb, requires_grad=False, device=self.device)
         trace = []
@@ -300,12 +299,15 @@ class PPO:
             sb = st.get("stream_b")
             if sb is None:
                 sb = st["stream_b"] = torch.cuda.Stream(params.device)
-            stream_b, ws_b = C.c_void_p(sb.cuda_stream), st["ws_b"]
+            stream_b, ws_b = sb.cuda_stream, st["ws_b"]
             if "enc_snap" not in st:
                 st["enc_snap"] = [torch.zeros(net.total, device=params.device) for _ in range(_SNAPSHOTS)]
             e0, e1 = net.e1w, net.std_off  # the encoder's weights and biases: one contiguous range
         else:
             sb, stream_b, ws_b = cur, stream, ws
+        params_p, grads_p, m_p, v_p, ws_p, ws_b_p, ctrl_p = (t.data_ptr()
+                                                             for t in (params, grads, m, v, ws, ws_b, ctrl))
+        adapt_lr = float(self.args.adaptation_module_learning_rate)
         # the adaptation chain's batch descriptor: the rows pointer of minibatch i must outlive the next C call
         batch_b = _abi.LrlPpoBatch()
         C.memmove(C.byref(batch_b), C.byref(batch), C.sizeof(batch))
@@ -320,14 +322,12 @@ class PPO:
             for i in range(nmb):
                 rows = indices[i * mb:(i + 1) * mb]
                 batch.rows = rows.data_ptr()
-                _abi.check(L.lrl_ppo_forward_backward(C.byref(net), ptr(params), ptr(grads), C.byref(batch),
-                                                      C.byref(hp), ptr(ws), ptr(ctrl), stream))
+                _abi.check(L.lrl_ppo_forward_backward(net, params_p, grads_p, batch, hp, ws_p, ctrl_p, stream))
                 if coll:
                     _all_reduce_(main)
                 st["steps"][0] += 1
-                _abi.check(L.lrl_ppo_optimizer_step(C.byref(net), ptr(params), ptr(grads), ptr(m), ptr(v),
-                                                    C.c_int64(st["steps"][0]), C.c_float(scale), C.byref(hp),
-                                                    ptr(ws), ptr(ctrl), stream))
+                _abi.check(L.lrl_ppo_optimizer_step(net, params_p, grads_p, m_p, v_p, st["steps"][0], scale, hp, ws_p,
+                                                    ctrl_p, stream))
                 if self.record_lr:
                     trace.append(ctrl[0].clone())
                 enc = None
@@ -336,21 +336,19 @@ class PPO:
                     if read_done[k % _SNAPSHOTS] is not None:
                         cur.wait_event(read_done[k % _SNAPSHOTS])
                     snap[e0:e1].copy_(params[e0:e1])
-                    enc = ptr(snap)
+                    enc = snap.data_ptr()
                     sb.wait_stream(cur)
                 batch_b.rows = rows.data_ptr()
                 # (a plain net — lrl.hlp's policy, which also turns overlap_adaptation off — has no adaptation phases)
                 for _ in range(0 if net.plain else self.args.num_adaptation_module_substeps):
-                    _abi.check(L.lrl_ppo_adaptation_forward_backward(C.byref(net), ptr(params), enc, ptr(grads),
-                                                                     C.byref(batch_b), ptr(ws_b), ptr(ctrl), stream_b))
+                    _abi.check(L.lrl_ppo_adaptation_forward_backward(net, params_p, enc, grads_p, batch_b, ws_b_p,
+                                                                     ctrl_p, stream_b))
                     if coll:
                         with torch.cuda.stream(sb):
                             _all_reduce_(adapt)
                     st["steps"][1] += 1
-                    _abi.check(L.lrl_ppo_adaptation_step(C.byref(net), ptr(params), ptr(grads), ptr(m), ptr(v),
-                                                         C.c_int64(st["steps"][1]),
-                                                         C.c_double(self.args.adaptation_module_learning_rate),
-                                                         C.c_float(scale), C.byref(hp), ptr(ctrl), stream_b))
+                    _abi.check(L.lrl_ppo_adaptation_step(net, params_p, grads_p, m_p, v_p, st["steps"][1], adapt_lr,
+                                                         scale, hp, ctrl_p, stream_b))
                 if sb is not cur:
                     ev = st["read_done_ev"][k % _SNAPSHOTS]
                     ev.record(sb)

@@ -4,7 +4,6 @@ Buffers keep the reference's [T, N, ...] shapes.  In the fused rollout path the 
 writes obs / priv / history / actions / values / log-probs / mu / sigma straight into row
 ``self.step`` (``lrl_rollout_store``), so ``add_transitions`` only has the env outputs left to copy.
 """
-import ctypes as C
 
 import torch
 
@@ -102,19 +101,16 @@ class RolloutStorage:
         if self._ws is None:
             self._ws = torch.empty(4096, device=self.device)
         lv = last_values.contiguous().float()
-        p = lambda t: C.c_void_p(t.data_ptr())
         stream = _abi.stream_of(self.rewards.device)
+        args = (self.rewards.data_ptr(), self.dones.data_ptr(), self.values.data_ptr(), lv.data_ptr(), T, N,
+                float(gamma), float(lam), self.returns.data_ptr(), self.advantages.data_ptr(), self._ws.data_ptr())
         if reduce_stats is None:
-            _abi.check(_abi.lib().lrl_gae(p(self.rewards), p(self.dones), p(self.values), p(lv), C.c_int32(T),
-                                          C.c_int32(N), C.c_float(gamma), C.c_float(lam), p(self.returns),
-                                          p(self.advantages), p(self._ws), stream))
+            _abi.check(_abi.lib().lrl_gae(*args, stream))
         else:
             stats = torch.empty(3, dtype=torch.float64, device=self.device)
-            _abi.check(_abi.lib().lrl_gae_partial(p(self.rewards), p(self.dones), p(self.values), p(lv),
-                                                  C.c_int32(T), C.c_int32(N), C.c_float(gamma), C.c_float(lam),
-                                                  p(self.returns), p(self.advantages), p(self._ws), p(stats), stream))
+            _abi.check(_abi.lib().lrl_gae_partial(*args, stats.data_ptr(), stream))
             stats = reduce_stats(stats)
-            _abi.check(_abi.lib().lrl_adv_normalize(p(self.advantages), C.c_int64(T * N), p(stats), stream))
+            _abi.check(_abi.lib().lrl_adv_normalize(self.advantages.data_ptr(), T * N, stats.data_ptr(), stream))
 
     def mini_batch_generator(self, num_mini_batches, num_epochs=8):
         batch_size = self.num_envs * self.num_transitions_per_env

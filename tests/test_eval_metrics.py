@@ -236,7 +236,7 @@ def test_new_symbols_resolve_and_abi_version_stays():
         assert getattr(L, name).restype is C.c_int32
     null = C.c_void_p()
     for call in (lambda: L.lrl_sim_metrics_enable(null, C.c_int32(1)), lambda: L.lrl_sim_metrics_clear(null, null),
-                 lambda: L.lrl_sim_metrics_tensors(null, null),
+                 lambda: L.lrl_sim_metrics_tensors(null, None),  # (lrl_metrics_view* out: a null struct pointer)
                  lambda: L.lrl_sim_metrics_reduce(null, C.c_int32(0), C.c_int32(0), null, null)):
         assert call() == -1  # LRL_E_INVALID on a null sim: no launch
 
