@@ -129,4 +129,70 @@ int gemm_last_path();
 // How a weight-gradient product (reduction over K rows, `groups` problems) is split: the split count.
 int gemm_pick_splits(int M, int N, int K, int groups);
 
+// false when the bf16-split families are switched off (LRL_GEMM_X6=0, lrl_debug_gemm_paths): the fp32 MFMA families
+// then take every product
+bool gemm_x6_enabled();
+// the smallest batch (M) of a forward product gemm_x6_kernel takes: below it the product runs on the fp32 MFMA
+constexpr int X6_MIN_M = 64;
+
+#ifdef __HIPCC__
+// ---- device helpers shared by the x6 GEMM families (lrl_gemm.hip) and the one-launch act (lrl_ppo.hip) ----
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef short bf16x8_t __attribute__((ext_vector_type(8)));
+constexpr int XBK = 16;  // k extent of an x6 step and of a plane image's rows
+
+__device__ __forceinline__ float elu_f(float x) { return x > 0.f ? x : expm1f(x); }
+// the device library's tanhf: an odd polynomial below |x| = 0.625, so small pre-activations keep their relative
+// accuracy (a bare 1 - 2 / (exp(2x) + 1) cancels there: half the digits are gone at |x| = 1e-3), and the function torch
+// itself evaluates on the device
+__device__ __forceinline__ float tanh_f(float x) { return tanhf(x); }
+// epilogue classes: a bias vector added before the activation / the layer input's activation output read as aux
+__host__ __device__ constexpr bool epi_bias(int e) { return e == EPI_BIAS || e == EPI_BIAS_ELU || e == EPI_BIAS_TANH; }
+__host__ __device__ constexpr bool epi_aux(int e) { return e == EPI_DELU || e == EPI_DTANH; }
+// the epilogue's value: v = the accumulator, bj = the column's bias, x = the aux operand (kernels of families without
+// an aux epilogue pass 0)
+template <int EPI>
+__device__ __forceinline__ float epi_apply(float v, float bj, float x) {
+  if constexpr (EPI == EPI_BIAS) return v + bj;
+  else if constexpr (EPI == EPI_BIAS_ELU) return elu_f(v + bj);
+  else if constexpr (EPI == EPI_BIAS_TANH) return tanh_f(v + bj);
+  else if constexpr (EPI == EPI_DELU) return x > 0.f ? v : v * (x + 1.f);
+  else if constexpr (EPI == EPI_DTANH) return v * (1.f - x * x);
+  else return v;
+}
+
+__device__ __forceinline__ uint32_t x6_hi_pair(uint32_t u0, uint32_t u1) {
+  return __builtin_amdgcn_perm(u1, u0, 0x07060302u);  // (u1 & 0xffff0000) | (u0 >> 16)
+}
+// (x0, x1) -> the packed bf16 pairs of their hi / mid / lo parts
+__device__ __forceinline__ void x6_split2(float x0, float x1, uint32_t& h, uint32_t& m, uint32_t& l) {
+  uint32_t u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
+  h = x6_hi_pair(u0, u1);
+  float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
+  u0 = __float_as_uint(r0);
+  u1 = __float_as_uint(r1);
+  m = x6_hi_pair(u0, u1);
+  r0 = r0 - __uint_as_float(u0 & 0xffff0000u);
+  r1 = r1 - __uint_as_float(u1 & 0xffff0000u);
+  l = x6_hi_pair(__float_as_uint(r0), __float_as_uint(r1));
+}
+// bf16 offset of 16-B chunk c of row r in a [R][16] plane image (chunk slots swapped in every other 8-row block: the
+// 16-lane groups of a ds_read_b128 operand read stay conflict-free)
+__device__ __forceinline__ int x6_off(int r, int c) { return r * XBK + 8 * (c ^ ((r >> 3) & 1)); }
+
+// One 32x32x16 step of the split product: c + a b from the hi / mid / lo planes a[0..2], b[0..2], as the six products
+// a2 b0, a1 b1, a0 b2, a1 b0, a0 b1, a0 b0 (smallest first) chained through c.  Every x6 family (x6, x6p, x6t, x6d)
+// and the one-launch act take their step from here over the same k order: that one order is what makes their results
+// bit-identical.
+__device__ __forceinline__ f32x16 x6_mma(const bf16x8_t (&a)[3], const bf16x8_t (&b)[3], f32x16 c) {
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
+  return c;
+}
+#endif  // __HIPCC__
+
 }  // namespace lrl

@@ -14,7 +14,6 @@
 
 namespace lrl {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #ifndef LRL_GBK
 #define LRL_GBK 16
@@ -76,25 +75,6 @@ static int tn_shape_tag(int M, int N, int groups) {
   return 0;
 }
 
-__device__ __forceinline__ float elu_f(float x) { return x > 0.f ? x : expm1f(x); }
-// the device library's tanhf: an odd polynomial below |x| = 0.625, so small pre-activations keep their relative
-// accuracy (a bare 1 - 2 / (exp(2x) + 1) cancels there: half the digits are gone at |x| = 1e-3), and the function torch
-// itself evaluates on the device
-__device__ __forceinline__ float tanh_f(float x) { return tanhf(x); }
-// epilogue classes: a bias vector added before the activation / the layer input's activation output read as aux
-__host__ __device__ constexpr bool epi_bias(int e) { return e == EPI_BIAS || e == EPI_BIAS_ELU || e == EPI_BIAS_TANH; }
-__host__ __device__ constexpr bool epi_aux(int e) { return e == EPI_DELU || e == EPI_DTANH; }
-// the epilogue's value: v = the accumulator, bj = the column's bias, x = the aux operand (kernels of families without
-// an aux epilogue pass 0)
-template <int EPI>
-__device__ __forceinline__ float epi_apply(float v, float bj, float x) {
-  if constexpr (EPI == EPI_BIAS) return v + bj;
-  else if constexpr (EPI == EPI_BIAS_ELU) return elu_f(v + bj);
-  else if constexpr (EPI == EPI_BIAS_TANH) return tanh_f(v + bj);
-  else if constexpr (EPI == EPI_DELU) return x > 0.f ? v : v * (x + 1.f);
-  else if constexpr (EPI == EPI_DTANH) return v * (1.f - x * x);
-  else return v;
-}
 
 // ---- dispatch: a runtime (layout, epilogue) pair to a template instantiation ----
 template <int V>
@@ -971,7 +951,6 @@ static int launch_glds_tn(const GemmP& p, int groups, hipStream_t st) {
 // the 16-lane groups of the ds_read_b128 operand reads conflict-free.
 // BM x BN tile (64 or 128 each), 4 waves in a 2 x 2 grid, wave tile (BM/2) x (BN/2) = TM x TN MFMA tiles;
 // BK = 16, two LDS stages, the next slice's global loads in flight under the current slice's MFMAs.
-constexpr int XBK = 16;
 #ifndef LRL_X6_PIPE
 #define LRL_X6_PIPE 1  // software-pipelined main loop (see gemm_x6_kernel)
 #endif
@@ -979,37 +958,6 @@ constexpr int XBK = 16;
 #define LRL_X6_PIPE_VALU 4  // VALU instructions scheduled after each MFMA of the pipelined loop
 #endif
 
-__device__ __forceinline__ uint32_t x6_hi_pair(uint32_t u0, uint32_t u1) {
-  return __builtin_amdgcn_perm(u1, u0, 0x07060302u);  // (u1 & 0xffff0000) | (u0 >> 16)
-}
-// (x0, x1) -> the packed bf16 pairs of their hi / mid / lo parts
-__device__ __forceinline__ void x6_split2(float x0, float x1, uint32_t& h, uint32_t& m, uint32_t& l) {
-  uint32_t u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
-  h = x6_hi_pair(u0, u1);
-  float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
-  u0 = __float_as_uint(r0);
-  u1 = __float_as_uint(r1);
-  m = x6_hi_pair(u0, u1);
-  r0 = r0 - __uint_as_float(u0 & 0xffff0000u);
-  r1 = r1 - __uint_as_float(u1 & 0xffff0000u);
-  l = x6_hi_pair(__float_as_uint(r0), __float_as_uint(r1));
-}
-__device__ __forceinline__ int x6_off(int r, int c) { return r * XBK + 8 * (c ^ ((r >> 3) & 1)); }
-
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-
-// One 32x32x16 step of the split product: c + a b from the hi / mid / lo planes a[0..2], b[0..2], as the six products
-// a2 b0, a1 b1, a0 b2, a1 b0, a0 b1, a0 b0 (smallest first) chained through c.  Every x6 family (x6, x6p, x6t, x6d)
-// takes its step from here over the same k order: that one order is what makes their results bit-identical.
-__device__ __forceinline__ f32x16 x6_mma(const bf16x8_t (&a)[3], const bf16x8_t (&b)[3], f32x16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-  return c;
-}
 
 template <int R, bool KC, bool KGATHER = false>
 struct X6Op {
@@ -1379,6 +1327,7 @@ static bool x6_enabled() {
   static const int on = env_switch("LRL_GEMM_X6", 1);
   return on != 0 && !(path_off() & 16);
 }
+bool gemm_x6_enabled() { return x6_enabled(); }
 
 static int try_x6d(const GemmP& p, int layout, int epi, int groups, int bm, int bn, hipStream_t st);
 static bool x6d_fits(const GemmP& p, int layout, int bm, int bn);
@@ -1402,7 +1351,7 @@ static bool x6_tile(const GemmP& p, int layout, int epi, int groups, int& bm, in
     bn = p.N <= 64 ? 64 : 128;
     return true;
   }
-  if (p.splits != 1 || p.N < 16 || p.M < 64 || epi == EPI_PARTIAL) return false;
+  if (p.splits != 1 || p.N < 16 || p.M < X6_MIN_M || epi == EPI_PARTIAL) return false;
   // measured (scripts/gemm_bench.py): one or two 16-k slices do not pay the split / staging set-up, and the
   // thin kernel (B in registers) stays faster for <= 32-wide outputs over k = 512 / 1024
   if (p.K < 32) return false;

@@ -371,41 +371,61 @@ struct ActHeadArgs {
   float* xa_out;  // ENC_ONLY: the [obs | latent | 0] rows, pitch xs
 };
 
-// rows [0, nrows) of src (pitch sld) -> dst (pitch dld), `cols` floats each, by the block's HEAD_THREADS
+// rows [0, nrows) of src (pitch sld) -> dst (pitch dld), `cols` floats each, by the block's NT
 // threads with 8 loads in flight per thread (float2 when both sides allow)
+template <int NT = HEAD_THREADS>
 __device__ __forceinline__ void copy_rows(const float* __restrict__ src, int64_t sld, float* __restrict__ dst,
                                           int64_t dld, int nrows, int cols, int t) {
   if (((((uintptr_t)src | (uintptr_t)dst) & 7) == 0) && (((sld | dld | cols) & 1) == 0)) {
     const int c2 = cols / 2, n = nrows * c2;
-    for (int i0 = t; i0 < n; i0 += 8 * HEAD_THREADS) {
+    for (int i0 = t; i0 < n; i0 += 8 * NT) {
       float2 v[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        const int i = i0 + u * HEAD_THREADS, r = i / c2, c = i - r * c2;
+        const int i = i0 + u * NT, r = i / c2, c = i - r * c2;
         if (i < n) v[u] = reinterpret_cast<const float2*>(src + r * sld)[c];
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        const int i = i0 + u * HEAD_THREADS, r = i / c2, c = i - r * c2;
+        const int i = i0 + u * NT, r = i / c2, c = i - r * c2;
         if (i < n) reinterpret_cast<float2*>(dst + r * dld)[c] = v[u];
       }
     }
   } else {
     const int n = nrows * cols;
-    for (int i0 = t; i0 < n; i0 += 8 * HEAD_THREADS) {
+    for (int i0 = t; i0 < n; i0 += 8 * NT) {
       float v[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        const int i = i0 + u * HEAD_THREADS, r = i / cols, c = i - r * cols;
+        const int i = i0 + u * NT, r = i / cols, c = i - r * cols;
         if (i < n) v[u] = src[r * sld + c];
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        const int i = i0 + u * HEAD_THREADS, r = i / cols, c = i - r * cols;
+        const int i = i0 + u * NT, r = i / cols, c = i - r * cols;
         if (i < n) dst[r * dld + c] = v[u];
       }
     }
   }
+}
+
+// One (row g, action j) of the rollout head: the noise (injected, or Box-Muller on the counter RNG, stream POLICY, keyed
+// by the global env id: pairs of actions share one Philox draw), the action into `act`; returns the log-prob term
+__device__ __forceinline__ float act_draw(const float* eps, int64_t row_offset, uint64_t seed, uint64_t counter, int g,
+                                          int j, int na, float m, float sd, float& act) {
+  float e;
+  if (eps) {
+    e = eps[(int64_t)g * na + j];
+  } else {
+    lrl_u32x4 u = lrl_philox((uint32_t)(row_offset + g), (uint32_t)counter, (LRL_RNG_POLICY << 16) ^ (uint32_t)(counter >> 32),
+                             (uint32_t)(j >> 1), seed);
+    const float u1 = fmaxf(lrl_u01(u.v[0]), 1e-7f), u2 = lrl_u01(u.v[1]);
+    const float rad = sqrtf(-2.f * logf(u1)), th = 6.283185307179586f * u2;
+    e = (j & 1) ? rad * sinf(th) : rad * cosf(th);
+  }
+  act = m + sd * e;
+  const float d = act - m;
+  return -(d * d) / (2.f * (sd * sd)) - logf(sd) - LOG_SQRT_2PI;
 }
 
 // rollout head: ACT_ROWS rows per workgroup (4096 envs -> 256 workgroups, one per CU: the kernel holds one workgroup
@@ -456,20 +476,9 @@ __global__ __launch_bounds__(HEAD_THREADS) void act_head_kernel(ActHeadArgs a) {
   // one thread per (row, action): sample + write; the per-row log-prob sum is formed after a barrier
   for (int i = t; i < nrows * na; i += HEAD_THREADS) {
     const int r = i / na, j = i - r * na, g = r0 + r;
-    float e;
-    if (a.eps) {
-      e = a.eps[(int64_t)g * na + j];
-    } else {  // Box-Muller on the counter RNG (stream POLICY): pairs of actions share one Philox draw
-      lrl_u32x4 u = lrl_philox((uint32_t)(a.row_offset + g), (uint32_t)a.counter, (LRL_RNG_POLICY << 16) ^ (uint32_t)(a.counter >> 32),
-                               (uint32_t)(j >> 1), a.seed);
-      const float u1 = fmaxf(lrl_u01(u.v[0]), 1e-7f), u2 = lrl_u01(u.v[1]);
-      const float rad = sqrtf(-2.f * logf(u1)), th = 6.283185307179586f * u2;
-      e = (j & 1) ? rad * sinf(th) : rad * cosf(th);
-    }
     const float m = MU[r][j], sd = a.stdv[j];
-    const float act = m + sd * e;
-    const float d = act - m;
-    MU[r][j] = -(d * d) / (2.f * (sd * sd)) - logf(sd) - LOG_SQRT_2PI;  // log-prob term (mu no longer needed)
+    float act;
+    MU[r][j] = act_draw(a.eps, a.row_offset, a.seed, a.counter, g, j, na, m, sd, act);  // (mu no longer needed)
     a.actions[(int64_t)g * na + j] = act;
     if (a.mu) a.mu[(int64_t)g * na + j] = m;
     if (a.do_store) {
@@ -513,29 +522,50 @@ __global__ __launch_bounds__(HEAD_THREADS) void act_head_kernel(ActHeadArgs a) {
 
 // ---------------------------------------------------------------------------------------------------
 // Fused rollout act (PPO.act, ppo.py:62-74 -> actor_critic.py:137-147,170-173, + RolloutStorage.add_transitions,
-// rollout_storage.py:57-71): one workgroup carries FA_R = 16 env rows through the whole chain — encoder, actor / critic
-// bodies, heads, sampling, log-prob and the storage row — with every activation in LDS, so a rollout step's act is one
-// launch (the unfused chain is eight, each on its ~6-10 us load -> MFMA -> store floor at 4,096 rows).  The products
-// run on the fp32 MFMA (v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 accumulation): a wave owns a run of 16-column
-// output tiles; per 16-k chunk lane (i, q) = (lane & 15, lane >> 4) reads A[i][k0 + 4q .. +3] from LDS (one b128) and,
-// per tile, the 4 weights W[n][k0 + 4q .. +3] of its output column n straight from L2 (the next chunk's loads are in
-// flight while this chunk's MFMAs run); step s of the chunk multiplies k = k0 + 4q + s.  16 rows per workgroup puts
-// 4,096 envs on 256 workgroups, one per CU (115 KB of LDS).
-constexpr int FA_R = 16, FA_THREADS = 256;
+// rollout_storage.py:57-71), act_fused_kernel, in two instances:
+//  * ENC_ONLY: the GEMM chain's first launch.  One workgroup carries FA_R = 16 env rows through the obs staging and
+//    the env-factor encoder and writes the X rows [obs | latent | 0] for the x6 products behind it.
+//  * the whole act in one launch.  One workgroup carries (a tile of OA_R = 32 env rows, one group: actor or critic)
+//    through the encoder, its group's body, its head and its share of the storage row, with every activation in LDS:
+//    no activation goes to global memory and a rollout step's act is one launch instead of five.
+// The encoder runs on the fp32 MFMA (v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 accumulation, k-sequential): a
+// wave owns a run of 16-column output tiles; per 32-k chunk lane (i, q) = (lane & 15, lane >> 4) reads
+// A[i][k0 + 8q .. +7] from LDS and, per tile, the 8 weights W[n][k0 + 8q .. +7] of its output column n straight from L2
+// (FA_D chunks in flight); the 32-row instance multiplies both 16-row blocks against each weight register set.
+// The bodies of the one-launch act run as the chain's x6 products do (lrl_gemm.hip): every operand element split into
+// hi / mid / lo bf16 parts, 16-k steps from k = 0, x6_mma's six products per step, epi_apply<EPI_BIAS_ELU> — so each
+// output goes through the chain's instruction sequence and has its bits.  The activations (X, H1, H2) live in LDS as
+// plane images in gemm_x6_kernel's layout ([32][16] bf16 per plane and 16-k slice, x6_off), so an A operand is one
+// ds_read_b128 per plane and a layer needs no barrier inside it; a wave owns a run of 32-column output tiles and reads
+// its B operand — fp32 weights W[n][k], each element used by this wave only — from L2 into registers, splits it there
+// and feeds x6_mma (oa_tiles).  H3 is written as fp32 for the heads.
+constexpr int FA_R = 16, FA_THREADS = 256;  // ENC_ONLY: rows and threads per workgroup
 constexpr int FA_D = 2;       // weight chunks (32 k each) in flight per wave: the L2 round trip over the MFMA work
-constexpr int FA_XP = 260;    // X / he1 / h3 pitch (widths <= 256) + 4: conflict-free b128 row reads
-constexpr int FA_BIGP = 1028; // h1 pitch (2 x ac_h0 <= 1024)
-constexpr int FA_MIDP = 516;  // h2 pitch (2 x ac_h1 <= 512); priv / he2 use narrower pitches in the same region
-constexpr int FA_HW_FLOATS = (HEAD_NA + 1) * HEAD_W;  // the heads' weights, staged at the start
-constexpr int FA_LDS_FLOATS = FA_R * (FA_XP + FA_BIGP + FA_MIDP) + FA_HW_FLOATS;
-constexpr int FA_ENC_MIDP = 260;  // ENC_ONLY: priv [16][36] / he2 [16][enc_h1 + 4 <= 260]
+constexpr int FA_XP = 260;    // X / he1 pitch (widths <= 256) + 4: conflict-free b128 row reads
+constexpr int FA_ENC_MIDP = 260;  // priv [R][36] / he2 [R][enc_h1 + 4 <= 260]
 constexpr int FA_ENC_LDS_FLOATS = FA_R * (FA_XP + FA_XP + FA_ENC_MIDP);  // ENC_ONLY: X, he1, priv / he2 (49.9 KB)
+// The one-launch act's LDS (bytes; one extern array):
+//   region A [0, OA_A_BYTES): H1 planes (32 x ac_h0 <= 512, 6 B per element); before them the encoder's X / he1 /
+//     priv-he2 fp32 tiles (the last one ends 1.5 KB inside region B, dead before the X planes are written); after
+//     them H3 [32][OA_H3P] fp32
+//   region B [OA_A_BYTES, OA_LDS_BYTES): X planes (32 x xs <= 256), then H2 planes (32 x ac_h1 <= 256), then the
+//     head's weight rows and its mu / value-partial tile
+constexpr int OA_R = 32, OA_THREADS = 512;  // two waves per SIMD: one's MFMAs run under the other's split and ELU work
+constexpr int OA_MAX_H0 = 512, OA_MAX_H1 = 256, OA_MAX_XS = 256;
+constexpr int OA_PLANE = OA_R * XBK;    // bf16 elements of one plane image of a 16-k slice
+constexpr int OA_SLICE = 3 * OA_PLANE;  // hi, mid, lo
+constexpr int OA_A_BYTES = OA_R * OA_MAX_H0 * 6, OA_B_BYTES = OA_R * OA_MAX_H1 * 6;
+constexpr int OA_LDS_BYTES = OA_A_BYTES + OA_B_BYTES;  // 144 KB: one workgroup per CU
+constexpr int OA_H3P = HEAD_W + 1;  // H3 pitch: the heads read a row per lane
+static_assert(OA_R * OA_MAX_XS * 6 <= OA_B_BYTES && OA_R * OA_H3P * 4 <= OA_A_BYTES, "overlays");
+static_assert(OA_R * (2 * FA_XP + FA_ENC_MIDP) * 4 <= OA_A_BYTES + 2048, "encoder tiles");
+static_assert(((HEAD_NA * HEAD_W) + 2 * OA_R * 16) * 4 <= OA_B_BYTES, "head scratch");
 
 // Phase timers of the fused act (build with -DLRL_ACT_PROFILE, read with lrl_debug_act_profile): shader-clock cycles
-// per phase summed over workgroups (thread 0's view): stage, enc1..3, ac1..3, heads, sampling, storage copies
+// per phase summed over workgroups (thread 0's view): stage, enc1..3, X planes, ac1..3, heads, sampling, storage copies
 #ifdef LRL_ACT_PROFILE
 __device__ unsigned long long g_act_prof[12];
-#define FA_PROF_DECL unsigned long long fa_t = clock64();
+#define FA_PROF_INIT clock64()
 #define FA_PROF(i)                                                  \
   if (threadIdx.x == 0) {                                           \
     const unsigned long long t_ = clock64();                        \
@@ -543,7 +573,7 @@ __device__ unsigned long long g_act_prof[12];
     fa_t = t_;                                                      \
   }
 #else
-#define FA_PROF_DECL
+#define FA_PROF_INIT 0ull
 #define FA_PROF(i)
 #endif
 
@@ -551,36 +581,35 @@ typedef float fa_f32x4 __attribute__((ext_vector_type(4)));
 
 struct FaLayer {
   const float* A;   // LDS input rows
-  int pa, ga, K;    // pitch, column offset of group g's input (g * ga), k extent (multiple of 16, zero-padded)
-  const float* W;   // weights of group 0: [Nw rows][ldw], group g at W + g * gw
+  int pa, K;        // pitch, k extent (multiple of 32, zero-padded)
+  const float* W;   // weights [Nw rows][ldw]
   int ldw, Kw, Nw;  // row pitch, valid k (< Kw), valid rows (< Nw)
-  int64_t gw;
-  const float* b;   // bias of group 0 (group g at b + g * Nw)
-  float* C;         // LDS output: group g's column n at C[row * pc + coff + g * Ng + n]
-  int pc, coff, Ng, groups;
-  int elu, vec;     // ELU after the bias; vec: 16-B aligned weight rows with Kw % 4 == 0 (float4 loads)
+  const float* b;   // bias
+  float* C;         // LDS output: column n at C[row * pc + coff + n]
+  int pc, coff, Ng; // Ng: Nw rounded up to whole 16-column tiles
+  int elu;          // ELU after the bias
 };
 
-// NB column tiles of one group from t0; VEC: 16-B aligned weight rows (float4 loads), else dword loads.  The loads are
-// branch-free (addresses clamped into the weights, out-of-range elements zeroed by selection) so the compiler keeps the
-// FA_D chunks in flight with counted vmcnt waits instead of draining at every guarded load
-template <int NB, bool VEC>
+// NB column tiles from t0 for RB blocks of 16 rows; VEC: 16-B aligned weight rows (float4 loads), else dword loads.  The
+// loads are branch-free (addresses clamped into the weights, out-of-range elements zeroed by selection) so the compiler
+// keeps the FA_D chunks in flight with counted vmcnt waits instead of draining at every guarded load
+template <int NB, bool VEC, int RB>
 __device__ __forceinline__ void fa_tiles(const FaLayer& L, int t0) {
   const int lane = threadIdx.x & 63, i = lane & 15, q = lane >> 4;
-  const int tpg = L.Ng >> 4, g = t0 / tpg;  // a run never crosses a group (fa_layer)
-  const float* A = L.A + i * L.pa + g * L.ga + 8 * q;
-  const float* W = L.W + g * L.gw;
+  const float* A = L.A + i * L.pa + 8 * q;
   const float* rowp[NB];
   bool rok[NB];
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
-    const int n = (t0 + j - g * tpg) * 16 + i;
+    const int n = (t0 + j) * 16 + i;
     rok[j] = n < L.Nw;
-    rowp[j] = W + (int64_t)(rok[j] ? n : L.Nw - 1) * L.ldw;
+    rowp[j] = L.W + (int64_t)(rok[j] ? n : L.Nw - 1) * L.ldw;
   }
-  fa_f32x4 acc[NB];
+  fa_f32x4 acc[RB][NB];
 #pragma unroll
-  for (int j = 0; j < NB; ++j) acc[j] = fa_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int b = 0; b < RB; ++b)
+#pragma unroll
+    for (int j = 0; j < NB; ++j) acc[b][j] = fa_f32x4{0.f, 0.f, 0.f, 0.f};
   // per 32-k chunk lane (i, q) holds the 8 weights W[n][k0 + 8q .. +7] of each tile (a whole 128-B line per row and
   // chunk over the 4 lane groups) and A[i][k0 + 8q .. +7]; step s multiplies k = k0 + 8q + s
   auto load_b = [&](float4 (&bv)[NB][2], int k0) {
@@ -616,61 +645,66 @@ __device__ __forceinline__ void fa_tiles(const FaLayer& L, int t0) {
     for (int d = 0; d < FA_D; ++d) {
       const int c = c0 + d;
       if (c < nck) {
-        const float4 a0 = *reinterpret_cast<const float4*>(A + 32 * c);
-        const float4 a1 = *reinterpret_cast<const float4*>(A + 32 * c + 4);
-        const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+        float av[RB][8];
+#pragma unroll
+        for (int b = 0; b < RB; ++b) {
+          const float4 a0 = *reinterpret_cast<const float4*>(A + 16 * b * L.pa + 32 * c);
+          const float4 a1 = *reinterpret_cast<const float4*>(A + 16 * b * L.pa + 32 * c + 4);
+          av[b][0] = a0.x; av[b][1] = a0.y; av[b][2] = a0.z; av[b][3] = a0.w;
+          av[b][4] = a1.x; av[b][5] = a1.y; av[b][6] = a1.z; av[b][7] = a1.w;
+        }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
 #pragma unroll
           for (int j = 0; j < NB; ++j) {
             const float4& bq = ring[d][j][u >> 2];
-            const float b = (u & 3) == 0 ? bq.x : (u & 3) == 1 ? bq.y : (u & 3) == 2 ? bq.z : bq.w;
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], b, acc[j], 0, 0, 0);
+            const float bw = (u & 3) == 0 ? bq.x : (u & 3) == 1 ? bq.y : (u & 3) == 2 ? bq.z : bq.w;
+#pragma unroll
+            for (int b = 0; b < RB; ++b) acc[b][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[b][u], bw, acc[b][j], 0, 0, 0);
           }
         }
         load_b(ring[d], 32 * min(c + FA_D, nck - 1));  // (past the end: a harmless re-read of the last chunk)
       }
     }
   }
-  // C/D: column i of the tile, rows 4q .. 4q + 3 in the four registers
+  // C/D: column i of the tile, rows 4q .. 4q + 3 of each 16-row block in the four registers
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
-    const int n = (t0 + j - g * tpg) * 16 + i;
+    const int n = (t0 + j) * 16 + i;
     if (n < L.Nw) {
-      const float bias = L.b[g * L.Nw + n];
-      float* c = L.C + (4 * q) * L.pc + L.coff + g * L.Ng + n;
+      const float bias = L.b[n];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = acc[j][r] + bias;
-        if (L.elu) v = v > 0.f ? v : expm1f(v);
-        c[r * L.pc] = v;
+      for (int b = 0; b < RB; ++b) {
+        float* c = L.C + (16 * b + 4 * q) * L.pc + L.coff + n;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float v = acc[b][j][r] + bias;
+          if (L.elu) v = v > 0.f ? v : expm1f(v);
+          c[r * L.pc] = v;
+        }
       }
     }
   }
 }
 
-// one layer: the T = groups * Ng / 16 column tiles split into equal runs over the 4 waves (T < 4: one tile per wave).
-// NBC > 0: the run length known at compile time (the presets' widths), else dispatched on it
-template <int NBC, bool VEC>
+// one layer: the T = Ng / 16 column tiles split into equal runs over the workgroup's NW = 4 * RB waves (T < NW: one
+// tile per wave).  NBC > 0: the run length known at compile time (the presets' widths), else dispatched on it
+template <int NBC, bool VEC, int RB>
 __device__ __forceinline__ void fa_layer(const FaLayer& L) {
-  const int w = threadIdx.x >> 6, T = L.groups * (L.Ng >> 4);
-  const int tpw = T >= 4 ? T / 4 : 1;
+  constexpr int NW = 4 * RB;
+  const int w = threadIdx.x >> 6, T = L.Ng >> 4;
+  const int tpw = T >= NW ? T / NW : 1;
   if (w * tpw >= T) return;
   const int t0 = w * tpw;
-  if constexpr (NBC == 16) {
-    fa_tiles<8, VEC>(L, t0);
-    fa_tiles<8, VEC>(L, t0 + 8);
-  } else if constexpr (NBC > 0) {
-    fa_tiles<NBC, VEC>(L, t0);
+  if constexpr (NBC > 0) {
+    fa_tiles<NBC, VEC, RB>(L, t0);
   } else {
     switch (tpw) {
-      case 1: fa_tiles<1, VEC>(L, t0); break;
-      case 2: fa_tiles<2, VEC>(L, t0); break;
-      case 4: fa_tiles<4, VEC>(L, t0); break;
-      case 8: fa_tiles<8, VEC>(L, t0); break;
-      case 16: fa_tiles<8, VEC>(L, t0); fa_tiles<8, VEC>(L, t0 + 8); break;
+      case 1: fa_tiles<1, VEC, RB>(L, t0); break;
+      case 2: fa_tiles<2, VEC, RB>(L, t0); break;
+      case 4: fa_tiles<4, VEC, RB>(L, t0); break;
       default:
-        for (int t = t0; t < t0 + tpw; ++t) fa_tiles<1, VEC>(L, t);
+        for (int t = t0; t < t0 + tpw; ++t) fa_tiles<1, VEC, RB>(L, t);
     }
   }
 }
@@ -680,7 +714,7 @@ struct FusedActArgs {
   lrl_ppo_net net;
   const float *obs, *priv, *hist, *eps;
   int n, xs;
-  uint32_t vec;  // bit l: float4 weight loads allowed for layer l (FA_L_*)
+  uint32_t vec;  // bit l: float4 weight loads allowed for layer l (e2, e3, w1, w2, w3 = bits 1 .. 5)
   uint64_t seed, counter;
   int64_t row_offset;
   float *actions, *mu, *values, *logp;
@@ -689,149 +723,343 @@ struct FusedActArgs {
   float* xa_out;  // ENC_ONLY: the [obs | latent | 0] rows, pitch xs
 };
 
-// PRESET: the presets' network (18 -> 256 -> 128 -> 18 encoder, 2 x (64 -> 512 -> 256 -> 128) bodies, aligned weights):
-// every layer's run length and load width fixed at compile time; otherwise dispatched per layer.
-// ENC_ONLY: the rollout act's first four launches in one (ppo_prep_kernel's obs rows and the env-factor encoder's
-// three products): the X rows [obs | latent | 0] go to a.xa_out for the actor / critic chain, in FA_ENC_LDS_FLOATS
-template <bool PRESET, bool ENC_ONLY = false>
-__global__ __launch_bounds__(FA_THREADS) void act_fused_kernel(FusedActArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float fa_lds[];
-  float* X = fa_lds;                     // [16][FA_XP]: obs | latent | 0
-  float* BIG = X + FA_R * FA_XP;         // he1 [16][FA_XP], h1 [16][FA_BIGP], h3 [16][FA_XP]
-  float* MID = BIG + FA_R * (ENC_ONLY ? FA_XP : FA_BIGP);  // priv [16][36], he2 [16][enc_h1 + 4], h2 [16][FA_MIDP]
-  float* HW = MID + FA_R * FA_MIDP;      // [NA + 1][HEAD_W]: w4a rows, then w4c
-  FA_PROF_DECL
+// Obs staging and the env-factor encoder for 16 * RB rows from r0: X = [obs | latent | 0] (pitch FA_XP, zero rows past
+// n), through he1 [.][FA_XP] and MID (priv [.][36], then he2 [.][enc_h1 + 4]).  Ends behind a barrier.
+template <bool PRESET, int RB>
+__device__ __forceinline__ void fa_encoder(const FusedActArgs& a, float* X, float* HE1, float* MID, int r0, int nrows,
+                                           unsigned long long& fa_t) {
+  constexpr int R = 16 * RB, NT = 256 * RB;  // (the 32-row instance runs in the one-launch act's 512 threads)
   const lrl_ppo_net& nt = a.net;
-  const int t = threadIdx.x, r0 = blockIdx.x * FA_R, nrows = min(FA_R, a.n - r0);
+  const int t = threadIdx.x;
   const int no = nt.num_obs, np = nt.num_priv, PP = 36, EP2 = nt.enc_h1 + 4;
   // stage obs (zero padding and rows past n) and priv (k padded to 32)
-  for (int e = t; e < FA_R * a.xs; e += FA_THREADS) {
+  for (int e = t; e < R * a.xs; e += NT) {
     const int r = e / a.xs, c = e - r * a.xs;
     X[r * FA_XP + c] = (r < nrows && c < no) ? a.obs[(int64_t)(r0 + r) * no + c] : 0.f;
   }
-  for (int e = t; e < FA_R * 32; e += FA_THREADS) {
+  for (int e = t; e < R * 32; e += NT) {
     const int r = e >> 5, c = e & 31;
     MID[r * PP + c] = (r < nrows && c < np) ? a.priv[(int64_t)(r0 + r) * np + c] : 0.f;
   }
-  if constexpr (!ENC_ONLY)
-    for (int e = t; e < FA_HW_FLOATS; e += FA_THREADS)
-      HW[e] = e < HEAD_NA * HEAD_W ? a.w[nt.w4a + e] : a.w[nt.w4c + (e - HEAD_NA * HEAD_W)];
   __syncthreads();
   FA_PROF(0)
   const float* w = a.w;
   FaLayer L;
   // env_factor_encoder: priv -> enc_h0 (ELU) -> enc_h1 (ELU) -> latent, the latent into X[:, no:]
-  L = FaLayer{MID, PP, 0, 32, w + nt.e1w, np, np, nt.enc_h0, 0, w + nt.e1b, BIG, FA_XP, 0, nt.enc_h0, 1, 1, 0};
-  fa_layer<PRESET ? 4 : 0, false>(L);
+  L = FaLayer{MID, PP, 32, w + nt.e1w, np, np, nt.enc_h0, w + nt.e1b, HE1, FA_XP, 0, nt.enc_h0, 1};
+  fa_layer<PRESET ? 4 / RB : 0, false, RB>(L);
   __syncthreads();
   FA_PROF(1)
-  L = FaLayer{BIG, FA_XP, 0, nt.enc_h0, w + nt.e2w, nt.enc_h0, nt.enc_h0, nt.enc_h1, 0, w + nt.e2b, MID, EP2, 0,
-              nt.enc_h1, 1, 1, (int)(a.vec >> 1) & 1};
-  if (PRESET || (a.vec & 2u)) fa_layer<PRESET ? 2 : 0, true>(L);
-  else fa_layer<0, false>(L);
+  L = FaLayer{HE1, FA_XP, nt.enc_h0, w + nt.e2w, nt.enc_h0, nt.enc_h0, nt.enc_h1, w + nt.e2b, MID, EP2, 0, nt.enc_h1, 1};
+  if (PRESET || (a.vec & 2u)) fa_layer<PRESET ? 2 / RB : 0, true, RB>(L);
+  else fa_layer<0, false, RB>(L);
   __syncthreads();
   FA_PROF(2)
-  L = FaLayer{MID, EP2, 0, nt.enc_h1, w + nt.e3w, nt.enc_h1, nt.enc_h1, nt.latent, 0, w + nt.e3b, X, FA_XP, no,
-              (nt.latent + 15) / 16 * 16, 1, 0, (int)(a.vec >> 2) & 1};
-  if (PRESET || (a.vec & 4u)) fa_layer<PRESET ? 1 : 0, true>(L);
-  else fa_layer<0, false>(L);
+  L = FaLayer{MID, EP2, nt.enc_h1, w + nt.e3w, nt.enc_h1, nt.enc_h1, nt.latent, w + nt.e3b, X, FA_XP, no,
+              (nt.latent + 15) / 16 * 16, 0};
+  if (PRESET || (a.vec & 4u)) fa_layer<PRESET ? 1 : 0, true, RB>(L);
+  else fa_layer<0, false, RB>(L);
   __syncthreads();
   FA_PROF(3)
-  if constexpr (ENC_ONLY) {  // (xs % 32 == 0: whole float4s of the row)
-    const int q4 = a.xs >> 2;
+}
+
+// One body layer of the one-launch act for this workgroup's group and 32 rows
+struct OaLayer {
+  const uint16_t* A;  // LDS planes of the input: slice s (k = 16 s ..) at A + s * OA_SLICE, plane pl at + pl * OA_PLANE
+  int K;              // k extent: a multiple of 32, the input zero from Kw on
+  const float* W;     // the group's weights [N][ldw]
+  int ldw, Kw, N;     // row pitch, valid k (< Kw), output width (a multiple of 32)
+  const float* b;     // the group's bias
+  uint16_t* Cp;       // LDS planes of the output, or nullptr:
+  float* Cf;          // fp32 output rows, pitch OA_H3P
+};
+
+// NB 32-column output tiles from t0, D 32-k chunks of weights in flight.  Per chunk lane (li, h) = (lane & 31, lane >> 5)
+// holds, per tile, W[n][k0 + 8h .. +7] (step 0) and W[n][k0 + 16 + 8h .. +7] (step 1) of its output column n:
+// gemm_x6_kernel's operand element for that lane, so a row's 128-B line is consumed whole over the chunk's two steps.
+// MODE 2: 16-B aligned weight rows of whole 32-k chunks (Kw = K; N is whole tiles): plain float4 loads; 1: 16-B aligned
+// rows, 0: dword loads — both branch-free with clamped addresses and out-of-range elements zeroed by selection, as fa_tiles
+template <int NB, int D, int MODE>
+__device__ __forceinline__ void oa_tiles(const OaLayer& L, int t0) {
+  const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
+  const float* rowp[NB];
+  bool rok[NB];
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    const int n = (t0 + j) * 32 + li;
+    rok[j] = n < L.N;
+    rowp[j] = L.W + (int64_t)(rok[j] ? n : L.N - 1) * L.ldw;
+  }
+  f32x16 acc[NB];
+#pragma unroll
+  for (int j = 0; j < NB; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+  auto load_b = [&](float4 (&bv)[NB][4], int k0) {
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int k = k0 + 16 * s + 8 * h;
+        if constexpr (MODE == 2) {
+          bv[j][2 * s] = *reinterpret_cast<const float4*>(rowp[j] + k);
+          bv[j][2 * s + 1] = *reinterpret_cast<const float4*>(rowp[j] + k + 4);
+        } else if constexpr (MODE == 1) {  // (Kw % 4 == 0: a float4 is wholly inside or wholly outside the row)
+          const int k1 = min(k, L.Kw - 4), k2 = min(k + 4, L.Kw - 4);
+          float4 v0 = *reinterpret_cast<const float4*>(rowp[j] + k1);
+          float4 v1 = *reinterpret_cast<const float4*>(rowp[j] + k2);
+          const bool o0 = rok[j] && k < L.Kw, o1 = rok[j] && k + 4 < L.Kw;
+          bv[j][2 * s] = o0 ? v0 : make_float4(0.f, 0.f, 0.f, 0.f);
+          bv[j][2 * s + 1] = o1 ? v1 : make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+          float v[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+            const float x = rowp[j][min(k + u, L.Kw - 1)];
+            v[u] = (rok[j] && k + u < L.Kw) ? x : 0.f;
+          }
+          bv[j][2 * s] = make_float4(v[0], v[1], v[2], v[3]);
+          bv[j][2 * s + 1] = make_float4(v[4], v[5], v[6], v[7]);
+        }
+      }
+  };
+  const int nck = L.K >> 5;
+  const uint16_t* Ap = L.A + x6_off(li, h);
+  float4 ring[D][NB][4];
+#pragma unroll
+  for (int d = 0; d < D; ++d) load_b(ring[d], 32 * min(d, nck - 1));
+  for (int c0 = 0; c0 < nck; c0 += D) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const int c = c0 + d;
+      if (c < nck) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          bf16x8_t av[3];
+#pragma unroll
+          for (int pl = 0; pl < 3; ++pl)
+            av[pl] = *reinterpret_cast<const bf16x8_t*>(Ap + (2 * c + s) * OA_SLICE + pl * OA_PLANE);
+#pragma unroll
+          for (int j = 0; j < NB; ++j) {
+            const float4 x0 = ring[d][j][2 * s], x1 = ring[d][j][2 * s + 1];
+            uint32_t hh[4], mm[4], ll[4];
+            x6_split2(x0.x, x0.y, hh[0], mm[0], ll[0]);
+            x6_split2(x0.z, x0.w, hh[1], mm[1], ll[1]);
+            x6_split2(x1.x, x1.y, hh[2], mm[2], ll[2]);
+            x6_split2(x1.z, x1.w, hh[3], mm[3], ll[3]);
+            uint4 vh = make_uint4(hh[0], hh[1], hh[2], hh[3]), vm = make_uint4(mm[0], mm[1], mm[2], mm[3]),
+                  vl = make_uint4(ll[0], ll[1], ll[2], ll[3]);
+            bf16x8_t bv[3];
+            bv[0] = *reinterpret_cast<bf16x8_t*>(&vh);
+            bv[1] = *reinterpret_cast<bf16x8_t*>(&vm);
+            bv[2] = *reinterpret_cast<bf16x8_t*>(&vl);
+            acc[j] = x6_mma(av, bv, acc[j]);
+          }
+        }
+        load_b(ring[d], 32 * min(c + D, nck - 1));  // (past the end: a harmless re-read of the last chunk)
+      }
+    }
+  }
+  // C/D: column li of the tile, rows 8q + 4h .. +3 in accumulator registers 4q .. 4q + 3 (gemm_x6_kernel's epilogue)
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    const int n = (t0 + j) * 32 + li;
+    if (n < L.N) {
+      const float bj = L.b[n];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int row0 = 8 * q + 4 * h;
+        float v[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = epi_apply<EPI_BIAS_ELU>(acc[j][4 * q + r], bj, 0.f);
+        if (L.Cp) {  // element (row, k = n) of the next layer's A planes
+          uint16_t* cp = L.Cp + (n >> 4) * OA_SLICE + (n & 7);
+#pragma unroll
+          for (int r = 0; r < 4; r += 2) {
+            uint32_t hh, mm, ll;
+            x6_split2(v[r], v[r + 1], hh, mm, ll);
+            const int o0 = x6_off(row0 + r, (n >> 3) & 1), o1 = x6_off(row0 + r + 1, (n >> 3) & 1);
+            cp[o0] = (uint16_t)hh;
+            cp[o1] = (uint16_t)(hh >> 16);
+            cp[OA_PLANE + o0] = (uint16_t)mm;
+            cp[OA_PLANE + o1] = (uint16_t)(mm >> 16);
+            cp[2 * OA_PLANE + o0] = (uint16_t)ll;
+            cp[2 * OA_PLANE + o1] = (uint16_t)(ll >> 16);
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) L.Cf[(row0 + r) * OA_H3P + n] = v[r];
+        }
+      }
+    }
+  }
+}
+
+// one body layer: the N / 32 column tiles split into runs over the 8 waves, a run taken two and one tile at a time
+template <int MODE>
+__device__ __forceinline__ void oa_layer(const OaLayer& L) {
+  const int w = threadIdx.x >> 6, T = L.N >> 5, tpw = (T + 7) >> 3;
+  int t = w * tpw;
+  const int t1 = min(T, t + tpw);
+  for (; t + 2 <= t1; t += 2) oa_tiles<2, 2, MODE>(L, t);
+  if (t < t1) oa_tiles<1, 4, MODE>(L, t);
+}
+
+// PRESET: the presets' encoder (18 -> 256 -> 128 -> 18, aligned weights): every encoder layer's run length and load
+// width fixed at compile time; otherwise dispatched per layer.
+// ENC_ONLY: the rollout act's first four launches in one (ppo_prep_kernel's obs rows and the env-factor encoder's
+// three products): the X rows [obs | latent | 0] go to a.xa_out for the actor / critic chain, in FA_ENC_LDS_FLOATS.
+// Otherwise the whole act: workgroup b takes row tile b / 2 and group b % 2 (0 actor, 1 critic; neighbours in the grid
+// sit on different XCDs, so an XCD's L2 serves one group's weights), in OA_LDS_BYTES
+template <bool PRESET, bool ENC_ONLY = false>
+__global__ __launch_bounds__(ENC_ONLY ? FA_THREADS : OA_THREADS) void act_fused_kernel(FusedActArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float fa_lds[];
+  unsigned long long fa_t = FA_PROF_INIT;
+  const lrl_ppo_net& nt = a.net;
+  const int t = threadIdx.x;
+  if constexpr (ENC_ONLY) {
+    float* X = fa_lds;                // [16][FA_XP]: obs | latent | 0
+    float* HE1 = X + FA_R * FA_XP;    // [16][FA_XP]
+    float* MID = HE1 + FA_R * FA_XP;  // priv [16][36], he2 [16][enc_h1 + 4]
+    const int r0 = blockIdx.x * FA_R, nrows = min(FA_R, a.n - r0);
+    fa_encoder<PRESET, 1>(a, X, HE1, MID, r0, nrows, fa_t);
+    const int q4 = a.xs >> 2;  // (xs % 32 == 0: whole float4s of the row)
     for (int e = t; e < nrows * q4; e += FA_THREADS) {
       const int r = e / q4, c = 4 * (e - r * q4);
       *reinterpret_cast<float4*>(a.xa_out + (int64_t)(r0 + r) * a.xs + c) = *reinterpret_cast<const float4*>(X + r * FA_XP + c);
     }
-    return;
-  }
-  // actor / critic bodies, both at once: [obs | latent] -> 2 x ac_h0 -> 2 x ac_h1 -> 2 x ac_h2 (ELU)
-  const int nx = no + nt.latent;
-  L = FaLayer{X, FA_XP, 0, a.xs, w + nt.w1, nx, nx, 2 * nt.ac_h0, 0, w + nt.b1, BIG, FA_BIGP, 0, 2 * nt.ac_h0, 1, 1,
-              (int)(a.vec >> 3) & 1};
-  if (PRESET || (a.vec & 8u)) fa_layer<PRESET ? 16 : 0, true>(L);
-  else fa_layer<0, false>(L);
-  __syncthreads();
-  FA_PROF(4)
-  L = FaLayer{BIG, FA_BIGP, nt.ac_h0, nt.ac_h0, w + nt.w2, nt.ac_h0, nt.ac_h0, nt.ac_h1, (int64_t)nt.ac_h1 * nt.ac_h0,
-              w + nt.b2, MID, FA_MIDP, 0, nt.ac_h1, 2, 1, (int)(a.vec >> 4) & 1};
-  if (PRESET || (a.vec & 16u)) fa_layer<PRESET ? 8 : 0, true>(L);
-  else fa_layer<0, false>(L);
-  __syncthreads();
-  FA_PROF(5)
-  L = FaLayer{MID, FA_MIDP, nt.ac_h1, nt.ac_h1, w + nt.w3, nt.ac_h1, nt.ac_h1, nt.ac_h2, (int64_t)nt.ac_h2 * nt.ac_h1,
-              w + nt.b3, BIG, FA_XP, 0, nt.ac_h2, 2, 1, (int)(a.vec >> 5) & 1};
-  if (PRESET || (a.vec & 32u)) fa_layer<PRESET ? 4 : 0, true>(L);
-  else fa_layer<0, false>(L);
-  __syncthreads();
-  FA_PROF(6)
-  // heads: thread (r, j) j < na: mu; (r, na): value — sequential fmaf over k, as act_head_kernel's mu
-  constexpr int NA = HEAD_NA;
-  float* MU = X;  // the obs tile is dead: [16][NA + 1] mu, then log-prob terms; value in column NA
-  if (t < FA_R * (NA + 1)) {
-    const int r = t / (NA + 1), j = t - r * (NA + 1);
-    const float* h = BIG + r * FA_XP + (j < NA ? 0 : HEAD_W);
-    const float* wr = HW + j * HEAD_W;  // (row NA: w4c)
-    float s = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < HEAD_W; ++k) s = fmaf(h[k], wr[k], s);
-    s += j < NA ? w[nt.b4a + j] : w[nt.b4c];
-    MU[r * 16 + j] = s;
-  }
-  __syncthreads();
-  FA_PROF(7)
-  const int64_t so = (int64_t)a.store_row * a.n;
-  if (t < FA_R * NA) {
-    const int r = t / NA, j = t - r * NA, g = r0 + r;
-    if (r < nrows) {
-      float e;
-      if (a.eps) {
-        e = a.eps[(int64_t)g * NA + j];
-      } else {  // Box-Muller on the counter RNG (stream POLICY), keyed by the global env id (as act_head_kernel)
-        lrl_u32x4 u = lrl_philox((uint32_t)(a.row_offset + g), (uint32_t)a.counter,
-                                 (LRL_RNG_POLICY << 16) ^ (uint32_t)(a.counter >> 32), (uint32_t)(j >> 1), a.seed);
-        const float u1 = fmaxf(lrl_u01(u.v[0]), 1e-7f), u2 = lrl_u01(u.v[1]);
-        const float rad = sqrtf(-2.f * logf(u1)), th = 6.283185307179586f * u2;
-        e = (j & 1) ? rad * sinf(th) : rad * cosf(th);
-      }
-      const float m = MU[r * 16 + j], sd = w[nt.std_off + j];
-      const float act = m + sd * e;
-      const float d = act - m;
-      MU[r * 16 + j] = -(d * d) / (2.f * (sd * sd)) - logf(sd) - LOG_SQRT_2PI;
-      a.actions[(int64_t)g * NA + j] = act;
-      if (a.mu) a.mu[(int64_t)g * NA + j] = m;
-      if (a.do_store) {
-        const int64_t o = (so + g) * NA + j;
-        a.store.actions[o] = act;
-        a.store.mu[o] = m;
-        a.store.sigma[o] = sd;
+  } else {
+    constexpr int NA = HEAD_NA;
+    uint8_t* lds = reinterpret_cast<uint8_t*>(fa_lds);
+    float* X = fa_lds;                // [32][FA_XP]
+    float* HE1 = X + OA_R * FA_XP;    // [32][FA_XP]
+    float* MID = HE1 + OA_R * FA_XP;  // priv [32][36], he2 [32][enc_h1 + 4]
+    uint16_t* H1 = reinterpret_cast<uint16_t*>(lds);               // planes, ac_h0 / 16 slices
+    float* H3 = fa_lds;                                            // [32][OA_H3P]
+    uint16_t* XP = reinterpret_cast<uint16_t*>(lds + OA_A_BYTES);  // X planes (xs / 16 slices), then H2 planes
+    float* HW = reinterpret_cast<float*>(lds + OA_A_BYTES);        // then the head: [NA | 1][HEAD_W] weight rows,
+    float* MU = HW + NA * HEAD_W;                                  // [32][16] mu / log-prob terms (actor),
+    float* VP = MU + OA_R * 16;                                    // [32][16] value partials (critic)
+    const int grp = blockIdx.x & 1, r0 = (blockIdx.x >> 1) * OA_R, nrows = min(OA_R, a.n - r0);
+    const int no = nt.num_obs, np = nt.num_priv;
+    const float* w = a.w;
+    fa_encoder<PRESET, 2>(a, X, HE1, MID, r0, nrows, fa_t);
+    // [obs | latent | 0] rows -> hi / mid / lo plane images (thread: 8 consecutive k of one row)
+    {
+      const int c8 = a.xs >> 3;
+      for (int e = t; e < OA_R * c8; e += OA_THREADS) {
+        const int r = e / c8, c = e - r * c8;
+        const float4 x0 = *reinterpret_cast<const float4*>(X + r * FA_XP + 8 * c);
+        const float4 x1 = *reinterpret_cast<const float4*>(X + r * FA_XP + 8 * c + 4);
+        uint32_t hh[4], mm[4], ll[4];
+        x6_split2(x0.x, x0.y, hh[0], mm[0], ll[0]);
+        x6_split2(x0.z, x0.w, hh[1], mm[1], ll[1]);
+        x6_split2(x1.x, x1.y, hh[2], mm[2], ll[2]);
+        x6_split2(x1.z, x1.w, hh[3], mm[3], ll[3]);
+        uint16_t* p = XP + (c >> 1) * OA_SLICE + x6_off(r, c & 1);
+        *reinterpret_cast<uint4*>(p) = make_uint4(hh[0], hh[1], hh[2], hh[3]);
+        *reinterpret_cast<uint4*>(p + OA_PLANE) = make_uint4(mm[0], mm[1], mm[2], mm[3]);
+        *reinterpret_cast<uint4*>(p + 2 * OA_PLANE) = make_uint4(ll[0], ll[1], ll[2], ll[3]);
       }
     }
-  }
-  __syncthreads();
-  if (t < nrows) {
-    const int g = r0 + t;
-    float lp = 0.f;
-    for (int j = 0; j < NA; ++j) lp += MU[t * 16 + j];
-    const float v = MU[t * 16 + NA];
-    if (a.values) a.values[g] = v;
-    if (a.logp) a.logp[g] = lp;
+    __syncthreads();
+    FA_PROF(4)
+    // this group's body: [obs | latent] -> ac_h0 -> ac_h1 -> ac_h2 (ELU), X -> H1 -> H2 as planes, H3 as fp32 (one
+    // copy of the layer code: the three layers differ in their arguments only)
+    const int nx = no + nt.latent;
+#pragma unroll 1
+    for (int l = 0; l < 3; ++l) {
+      OaLayer L;
+      if (l == 0)
+        L = OaLayer{XP, a.xs, w + nt.w1 + (int64_t)grp * nt.ac_h0 * nx, nx, nx, nt.ac_h0, w + nt.b1 + grp * nt.ac_h0, H1, nullptr};
+      else if (l == 1)
+        L = OaLayer{H1, nt.ac_h0, w + nt.w2 + (int64_t)grp * nt.ac_h1 * nt.ac_h0, nt.ac_h0, nt.ac_h0, nt.ac_h1,
+                    w + nt.b2 + grp * nt.ac_h1, XP, nullptr};
+      else
+        L = OaLayer{XP, nt.ac_h1, w + nt.w3 + (int64_t)grp * nt.ac_h2 * nt.ac_h1, nt.ac_h1, nt.ac_h1, nt.ac_h2,
+                    w + nt.b3 + grp * nt.ac_h2, nullptr, H3};
+      if (!((a.vec >> (3 + l)) & 1u)) oa_layer<0>(L);
+      else if (L.Kw == L.K) oa_layer<2>(L);
+      else oa_layer<1>(L);
+      __syncthreads();
+      FA_PROF(5 + l)
+    }
+    // heads, as act_head_kernel's: mu a sequential fmaf over k; the value 16 partial sums over k-sixteenths joined by
+    // the pairwise tree.  The actor's workgroup writes actions, mu, sigma and log-prob, the critic's the value
+    const int64_t so = (int64_t)a.store_row * a.n;
+    if (grp == 0) {
+      for (int e = t; e < NA * HEAD_W; e += OA_THREADS) HW[e] = w[nt.w4a + e];
+      __syncthreads();
+      for (int e = t; e < OA_R * NA; e += OA_THREADS) {
+        const int r = e & (OA_R - 1), j = e / OA_R;
+        float s = 0.f;
+        for (int k = 0; k < HEAD_W; ++k) s = fmaf(H3[r * OA_H3P + k], HW[j * HEAD_W + k], s);
+        MU[r * 16 + j] = s + w[nt.b4a + j];
+      }
+      __syncthreads();
+      FA_PROF(8)
+      for (int i = t; i < nrows * NA; i += OA_THREADS) {
+        const int r = i / NA, j = i - r * NA, g = r0 + r;
+        const float m = MU[r * 16 + j], sd = w[nt.std_off + j];
+        float act;
+        MU[r * 16 + j] = act_draw(a.eps, a.row_offset, a.seed, a.counter, g, j, NA, m, sd, act);
+        a.actions[(int64_t)g * NA + j] = act;
+        if (a.mu) a.mu[(int64_t)g * NA + j] = m;
+        if (a.do_store) {
+          const int64_t o = (so + g) * NA + j;
+          a.store.actions[o] = act;
+          a.store.mu[o] = m;
+          a.store.sigma[o] = sd;
+        }
+      }
+      __syncthreads();
+      if (t < nrows) {
+        const int g = r0 + t;
+        float lp = 0.f;
+        for (int j = 0; j < NA; ++j) lp += MU[t * 16 + j];
+        if (a.logp) a.logp[g] = lp;
+        if (a.do_store) a.store.logp[so + g] = lp;
+      }
+    } else {
+      for (int e = t; e < HEAD_W; e += OA_THREADS) HW[e] = w[nt.w4c + e];
+      __syncthreads();
+      for (int e = t; e < OA_R * 16; e += OA_THREADS) {
+        const int r = e & (OA_R - 1), q = e / OA_R;
+        float s = 0.f;
+        for (int k = q * (HEAD_W / 16); k < (q + 1) * (HEAD_W / 16); ++k) s = fmaf(H3[r * OA_H3P + k], HW[k], s);
+        VP[r * 16 + q] = s;
+      }
+      __syncthreads();
+      FA_PROF(8)
+      if (t < nrows) {
+        const int g = r0 + t;
+        float vs[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) vs[q] = VP[t * 16 + q];
+#pragma unroll
+        for (int wd = 8; wd >= 1; wd /= 2)  // pairwise tree, fixed order
+#pragma unroll
+          for (int q = 0; q < wd; ++q) vs[q] = vs[2 * q] + vs[2 * q + 1];
+        const float v = vs[0] + w[nt.b4c];
+        if (a.values) a.values[g] = v;
+        if (a.do_store) a.store.values[so + g] = v;
+      }
+    }
+    FA_PROF(9)
+    // obs / priv / history rows of this tile into storage row `store_row`: obs and the first 16 history rows by the
+    // actor's workgroup, priv and the other history rows by the critic's
     if (a.do_store) {
-      a.store.values[so + g] = v;
-      a.store.logp[so + g] = lp;
+      const int64_t b = so + r0;
+      if (grp == 0) copy_rows<OA_THREADS>(a.obs + (int64_t)r0 * no, no, a.store.obs + b * no, no, nrows, no, t);
+      else copy_rows<OA_THREADS>(a.priv + (int64_t)r0 * np, np, a.store.priv + b * np, np, nrows, np, t);
+      if (a.hist && a.store.hist) {
+        const int hd = a.store.hist_dim, ld = a.store.hist_ld > hd ? a.store.hist_ld : hd;
+        const int h0 = grp * (OA_R / 2), hn = min(nrows, h0 + OA_R / 2) - h0;
+        if (hn > 0) copy_rows<OA_THREADS>(a.hist + (int64_t)(r0 + h0) * hd, hd, a.store.hist + (b + h0) * ld, ld, hn, hd, t);
+      }
     }
+    FA_PROF(10)
   }
-  FA_PROF(8)
-  if (a.do_store) {  // obs / priv / history rows of this tile into storage row `store_row`
-    const int64_t b = so + r0;
-    copy_rows(a.obs + (int64_t)r0 * no, no, a.store.obs + b * no, no, nrows, no, t);
-    copy_rows(a.priv + (int64_t)r0 * np, np, a.store.priv + b * np, np, nrows, np, t);
-    if (a.hist && a.store.hist) {
-      const int hd = a.store.hist_dim, ld = a.store.hist_ld > hd ? a.store.hist_ld : hd;
-      copy_rows(a.hist + (int64_t)r0 * hd, hd, a.store.hist + b * ld, ld, nrows, hd, t);
-    }
-  }
-  FA_PROF(9)
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1587,22 +1815,21 @@ static bool act_planes_on() {
   return e && e[0] == '1' && gemm_x6p_enabled();
 }
 
-// The envelope of act_fused_kernel (LDS pitches, tile runs that never cross a group): of the whole act (`body`), or of
-// its encoder part alone, which writes X for the GEMM chain.
+// The envelope of act_fused_kernel: of its encoder part (LDS pitches, whole tile runs per wave), which alone writes X
+// for the GEMM chain, and with `body` of the whole act (the plane regions of its LDS, whole 32-column tiles and 32-k
+// chunks in every body layer).
 static bool fused_envelope(const lrl_ppo_net& n, bool body) {
-  auto run_ok = [](int groups, int Ng) {  // fa_layer: equal runs per wave inside one group
+  auto run_ok = [](int Ng) {  // fa_layer: equal runs per wave
     if (Ng % 16) return false;
-    const int T = groups * (Ng / 16), tpg = Ng / 16;
-    const int tpw = T >= 4 ? T / 4 : 1;
-    if (T >= 4 && T % 4) return false;
-    return tpg % std::min(tpw, 8) == 0;
+    const int T = Ng / 16;
+    return T < 4 || T % 4 == 0;
   };
   if (!(xs_of(n) % 32 == 0 && xs_of(n) <= 256 && n.num_priv <= 32 && n.enc_h0 <= 256 && n.enc_h0 % 32 == 0 &&
-        n.enc_h1 % 32 == 0 && n.enc_h1 + 4 <= (body ? FA_MIDP : FA_ENC_MIDP) && n.latent <= 32 && run_ok(1, n.enc_h0) &&
-        run_ok(1, n.enc_h1) && run_ok(1, (n.latent + 15) / 16 * 16)))
+        n.enc_h1 % 32 == 0 && n.enc_h1 + 4 <= FA_ENC_MIDP && n.latent <= 32 && run_ok(n.enc_h0) && run_ok(n.enc_h1)))
     return false;
-  return !body || (n.ac_h0 % 32 == 0 && n.ac_h1 % 32 == 0 && 2 * n.ac_h0 <= 1024 && 2 * n.ac_h1 <= 512 &&
-                   2 * n.ac_h2 <= 256 && run_ok(1, 2 * n.ac_h0) && run_ok(2, n.ac_h1) && run_ok(2, n.ac_h2));
+  auto run8_ok = [](int Ng) { return Ng / 16 < 8 || (Ng / 16) % 8 == 0; };  // its encoder's runs over 8 waves
+  return !body || (run8_ok(n.enc_h0) && run8_ok(n.enc_h1) && xs_of(n) <= OA_MAX_XS && n.num_obs + n.latent >= 4 && n.ac_h0 % 32 == 0 && n.ac_h0 <= OA_MAX_H0 &&
+                   n.ac_h1 % 32 == 0 && n.ac_h1 <= OA_MAX_H1 && n.ac_h2 == HEAD_W && n.num_actions == HEAD_NA);
 }
 // LRL_ACT_ENC_FUSED=0: the prep kernel + three GEMM launches instead of the kernel's encoder part (read per call so a
 // test can switch it inside one process)
@@ -1610,28 +1837,42 @@ static bool act_enc_fused(const lrl_ppo_net& n) {
   const char* e = getenv("LRL_ACT_ENC_FUSED");
   return !(e && e[0] == '0') && fused_envelope(n, false);
 }
-// LRL_ACT_FUSED=1 selects the one-launch act over the GEMM chain (A/B timing and the tests that compare the two; read
-// per call): off by default until it measures faster than the chain
-static bool fused_act_fits(const lrl_ppo_net& n) {
+// The rows at which the one-launch act is the default (the measured table is in DESIGN.md §9).  The kernel holds one
+// workgroup per CU (144 KB of LDS) and a workgroup takes about 58 us whatever the grid, so the launch costs one such
+// round per 256 workgroups = 4,096 rows on the MI355X's 256 CUs: above that a second round starts and the chain, whose
+// cost grows with the activations alone, is faster; below 2,048 rows the chain's five launches are shorter than one round.
+constexpr int ACT_FUSED_MIN_ROWS = 2048, ACT_FUSED_MAX_ROWS = 4096;
+// The one-launch act or the GEMM chain (LRL_ACT_FUSED read per call: A/B timing and the tests that compare the two).
+// The one-launch act computes what the chain computes where the chain's body products run on gemm_x6_kernel, that is
+// from X6_MIN_M rows and with the bf16-split families on: outside that, and outside the kernel's envelope, every
+// setting takes the chain.  Inside, LRL_ACT_FUSED=0 takes the chain, =1 the one-launch act, and unset the one-launch
+// act from ACT_FUSED_MIN_ROWS to ACT_FUSED_MAX_ROWS rows.
+static bool fused_act_fits(const lrl_ppo_net& n, int rows) {
   const char* e = getenv("LRL_ACT_FUSED");
-  return e && e[0] == '1' && fused_envelope(n, true);
+  if (e && e[0] == '0') return false;
+  if (rows < X6_MIN_M || !gemm_x6_enabled() || !fused_envelope(n, true)) return false;
+  return (e && e[0] == '1') || (rows >= ACT_FUSED_MIN_ROWS && rows <= ACT_FUSED_MAX_ROWS);
 }
 // Launch act_fused_kernel, whole (`body`) or its encoder part: the float4 bits of the weight rows it reads, and the
-// instance specialised for the presets' widths where they and every bit hold.
+// instance specialised for the presets' encoder widths where they and its bits hold.
 static void launch_act_fused(FusedActArgs& fa, bool body, hipStream_t st) {
   const lrl_ppo_net& n = fa.net;
   auto al = [&](int64_t off, int ld) { return (reinterpret_cast<uintptr_t>(fa.w + off) & 15) == 0 && ld % 4 == 0; };
   fa.vec = (al(n.e2w, n.enc_h0) ? 2u : 0u) | (al(n.e3w, n.enc_h1) ? 4u : 0u);
   if (body)
     fa.vec |= (al(n.w1, n.num_obs + n.latent) ? 8u : 0u) | (al(n.w2, n.ac_h0) ? 16u : 0u) | (al(n.w3, n.ac_h1) ? 32u : 0u);
-  const bool preset = n.enc_h0 == 256 && n.enc_h1 == 128 && n.latent <= 32 &&
-                      (body ? n.ac_h0 == 512 && n.ac_h1 == 256 && n.ac_h2 == 128 && fa.vec == 62u : fa.vec == 6u);
-  const dim3 grid((fa.n + FA_R - 1) / FA_R), block(FA_THREADS);
-  const size_t lds = (body ? FA_LDS_FLOATS : FA_ENC_LDS_FLOATS) * sizeof(float);
-  if (body && preset) hipLaunchKernelGGL(act_fused_kernel<true>, grid, block, lds, st, fa);
-  else if (body) hipLaunchKernelGGL(act_fused_kernel<false>, grid, block, lds, st, fa);
-  else if (preset) hipLaunchKernelGGL((act_fused_kernel<true, true>), grid, block, lds, st, fa);
-  else hipLaunchKernelGGL((act_fused_kernel<false, true>), grid, block, lds, st, fa);
+  const bool preset = n.enc_h0 == 256 && n.enc_h1 == 128 && n.latent <= 32 && (fa.vec & 6u) == 6u;
+  const dim3 block(body ? OA_THREADS : FA_THREADS);
+  if (body) {
+    const dim3 grid(2 * ((fa.n + OA_R - 1) / OA_R));
+    if (preset) hipLaunchKernelGGL(act_fused_kernel<true>, grid, block, OA_LDS_BYTES, st, fa);
+    else hipLaunchKernelGGL(act_fused_kernel<false>, grid, block, OA_LDS_BYTES, st, fa);
+  } else {
+    const dim3 grid((fa.n + FA_R - 1) / FA_R);
+    const size_t lds = FA_ENC_LDS_FLOATS * sizeof(float);
+    if (preset) hipLaunchKernelGGL((act_fused_kernel<true, true>), grid, block, lds, st, fa);
+    else hipLaunchKernelGGL((act_fused_kernel<false, true>), grid, block, lds, st, fa);
+  }
 }
 
 extern "C" int64_t lrl_ppo_act_workspace_bytes(const lrl_ppo_net* net, int32_t n) {
@@ -1678,11 +1919,10 @@ extern "C" int32_t lrl_ppo_act(const lrl_ppo_net* net, const float* params, cons
   // (a plain net — priv / hist may be NULL: they are only copied into the storage row when given — is the same chain
   // with no encoder, no planes and tanh; the fused kernel is built around the presets' encoder and is not taken)
   const bool full = !nt.plain;
-  if (full && fused_act_fits(nt)) {  // one launch: act_fused_kernel
+  if (full && fused_act_fits(nt, n)) {  // one launch: act_fused_kernel
     static const bool ok = [] {
       auto set = [](const void* f) {
-        return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, FA_LDS_FLOATS * sizeof(float)) ==
-               hipSuccess;
+        return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, OA_LDS_BYTES) == hipSuccess;
       };
       return set(reinterpret_cast<const void*>(act_fused_kernel<true>)) &&
              set(reinterpret_cast<const void*>(act_fused_kernel<false>));

@@ -1,6 +1,6 @@
 """Phase breakdown of the one-launch act (act_fused_kernel; build with `make -C rapid-locomotion-rl_amd/csrc
 liblrl_prof.so PROF_DEFS=-DLRL_ACT_PROFILE`, run with LRL_LIB=<that build> LRL_ACT_FUSED=1): shader-clock cycles per
-workgroup and act for each phase, 4096 rows, the preset network.  usage: python scripts/act_profile.py [acts]"""
+workgroup and act for each phase (the mean over the actor's and the critic's workgroups), 4096 rows, the preset network.  usage: python scripts/act_profile.py [acts]"""
 import ctypes as C
 import os
 import sys
@@ -33,9 +33,9 @@ for i in range(K):
 ev1.record()
 torch.cuda.synchronize()
 L.lrl_debug_act_profile(buf, 0)
-wgs = (n + 15) // 16
-names = ["stage", "enc1", "enc2", "enc3", "ac1", "ac2", "ac3", "heads", "sample", "storage"]
-tot = sum(buf[i] for i in range(10))
+wgs = 2 * ((n + 31) // 32)  # (32-row tile, group) workgroups
+names = ["stage", "enc1", "enc2", "enc3", "xplanes", "ac1", "ac2", "ac3", "heads", "sample", "storage"]
+tot = sum(buf[i] for i in range(len(names)))
 print(f"act {ev0.elapsed_time(ev1) / K * 1e3:.1f} us per launch (events, {K} launches)")
 for i, nm in enumerate(names):
     print(f"{nm:8s} {buf[i] / (wgs * K):10.0f} cycles/WG  {100 * buf[i] / max(tot, 1):5.1f} %")
