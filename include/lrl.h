@@ -976,4 +976,8 @@ double lrl_np_sum_f64(const double* a, int64_t n);
 #ifdef __cplusplus
 }
 #endif
+
+/* the depth encoder's entry points (lrl_vision_*), part of this ABI, in a header of their own */
+#include "lrl_vision.h"
+
 #endif /* LRL_H_ */

@@ -1066,6 +1066,13 @@ class LeggedRobotEnv:
         self._depth_launch(only_reset=self._depth_step % self._depth_interval != 0)
         self._depth_step += 1
 
+    @property
+    def depth_refreshed(self):
+        """True when the last step() redrew every env's depth image (every update_interval-th step; in between only the
+        envs that were reset are redrawn).  False before the first step and without a depth camera."""
+        return self._depth_cam is not None and self._depth_step > 0 and \
+            (self._depth_step - 1) % self._depth_interval == 0
+
     def render_depth(self, ids=False):
         """Redraw every env's depth image from the current state now (whatever the update interval) and return
         (``depth_images``, ids): the planar depth in metres, float32 [num_envs, H, W], clamped to Cfg.depth's

@@ -10,9 +10,13 @@ the actor (``ActorCritic.act_student_fused``, the native GEMM chain).  A constan
 camera of ``env.render()``: the collision model plus link capsules) as ``OUT.npz``, and ``OUT.gif`` when PIL is installed.
 ``--depth OUT`` gives every env the egocentric depth camera (lrl.config.add_depth_camera's defaults) and saves env 0's
 image after every policy step as ``OUT.npz``: ``depth`` float32 [T, H, W], metres.
+``--depth-encoder ENC.pt`` (scripts/distill_depth.py's ``depth_encoder_last.pt``; needs ``--weights`` of a policy trained
+with the 187-column height scan): the env is the rough trimesh with the scan and the depth camera on, and the policy acts
+on ``DepthDistiller.predict_obs(obs)`` — the scan columns it sees, now and in its observation history, are the encoder's
+output from the depth image, not the simulator's scan.
 
   python scripts/play.py [--robot mc|go1] [--weights ac_weights.pt] [--envs 64] [--steps 1000] [--vx 1.0] [--video OUT]
-                         [--depth OUT]
+                         [--depth OUT] [--depth-encoder ENC.pt]
 """
 import argparse
 import json
@@ -31,7 +35,7 @@ from lrl.history import HistoryWrapper  # noqa: E402
 from lrl.ppo.actor_critic import ActorCritic  # noqa: E402
 
 
-def load_env(robot, num_envs, device, depth=False):
+def load_env(robot, num_envs, device, depth=False, scan=False):
     cfg = lcfg.make_cfg()
     (lcfg.config_mini_cheetah if robot == "mc" else lcfg.config_go1)(cfg)
     dr = cfg.domain_rand
@@ -43,6 +47,9 @@ def load_env(robot, num_envs, device, depth=False):
         cfg.sim.physx.solver_type = int(os.environ["LRL_SOLVER_TYPE"])
     cfg.terrain.num_rows, cfg.terrain.num_cols, cfg.terrain.border_size = 3, 5, 0
     cfg.terrain.max_init_terrain_level = min(cfg.terrain.max_init_terrain_level, cfg.terrain.num_rows - 1)
+    if scan:  # the perceptive policy's env: rough trimesh, the height scan at the end of obs
+        cfg.terrain.mesh_type, cfg.terrain.measure_heights = "trimesh", True
+        cfg.env.num_observations = 42 + len(cfg.terrain.measured_points_x) * len(cfg.terrain.measured_points_y)
     if depth:
         lcfg.add_depth_camera(cfg)
     return HistoryWrapper(LeggedRobotEnv(device, cfg=cfg)), cfg
@@ -61,13 +68,37 @@ def load_policy(weights, cfg, device):
     return lambda ob: ac.act_student_fused(ob["obs"].contiguous(), ob["obs_history"])[0]
 
 
+def depth_observer(path, env, device):
+    """obs dict -> obs dict whose scan columns (in ``obs`` and, step by step, in a history of its own) are the depth
+    encoder's output (DepthDistiller.predict_obs)."""
+    from lrl import vision
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    enc = vision.DepthEncoder(ck["height"], ck["width"], ck["out_dim"], extra_dim=ck["extra_dim"], hidden=ck["hidden"],
+                              far=ck["far"])
+    enc.load_state_dict(ck["state_dict"], strict=True)
+    d = vision.DepthDistiller(env.env, enc.to(device), capacity=1)
+    hist = torch.zeros_like(env.obs_history)
+    n = env.env.num_obs
+
+    def observe(ob, done=None):
+        pred = d.predict_obs(ob["obs"])
+        if done is not None:
+            hist[done] = 0.0  # (HistoryWrapper.reset_idx)
+        hist.copy_(torch.cat([hist[:, n:], pred], 1))
+        return dict(ob, obs=pred, obs_history=hist)
+    return observe
+
+
 def play(robot="mc", weights=None, num_envs=64, steps=1000, vx=1.0, vy=0.0, wz=0.0, device="cuda:0", frames=None,
-         depth=None):
+         depth=None, depth_encoder=None):
     """``frames``: a list that receives env 0's rendered frame (numpy uint8 [240, 360, 4]) after every policy step;
-    ``depth``: a list that receives env 0's depth image (numpy float32 [H, W]) after every policy step."""
-    env, cfg = load_env(robot, num_envs, device, depth=depth is not None)
+    ``depth``: a list that receives env 0's depth image (numpy float32 [H, W]) after every policy step;
+    ``depth_encoder``: a saved DepthEncoder, the policy then acts on its prediction of the height scan."""
+    env, cfg = load_env(robot, num_envs, device, depth=depth is not None or depth_encoder is not None,
+                        scan=depth_encoder is not None)
     policy = load_policy(weights, cfg, device)
     e = env.env
+    observe = depth_observer(depth_encoder, env, device) if depth_encoder else None
 
     def command():
         e.commands[:, 0], e.commands[:, 1], e.commands[:, 2] = vx, vy, wz
@@ -80,11 +111,15 @@ def play(robot="mc", weights=None, num_envs=64, steps=1000, vx=1.0, vy=0.0, wz=0
             command()
             obs, rew, done, info = env.step(actions)
     vel = np.zeros((steps, num_envs, 3), np.float32)
+    if observe:
+        obs = observe(obs)
     for i in range(steps):
         with torch.no_grad():
             actions = policy(obs)
         command()
         obs, rew, done, info = env.step(actions)
+        if observe:
+            obs = observe(obs, done)
         vel[i, :, :2] = e.base_lin_vel[:, :2].cpu().numpy()
         vel[i, :, 2] = e.base_ang_vel[:, 2].cpu().numpy()
         if frames is not None:
@@ -106,10 +141,15 @@ def main():
     ap.add_argument("--plot", default=None)
     ap.add_argument("--video", default=None, metavar="OUT", help="write env 0's frames to OUT.npz (and OUT.gif)")
     ap.add_argument("--depth", default=None, metavar="OUT", help="write env 0's depth images to OUT.npz")
+    ap.add_argument("--depth-encoder", default=None, metavar="ENC.pt",
+                    help="act on the depth encoder's height scan (needs --weights of a policy trained with the scan)")
     a = ap.parse_args()
+    if a.depth_encoder and not a.weights:
+        ap.error("--depth-encoder needs --weights: the default checkpoint's policy has no height scan")
     frames = [] if a.video else None
     depth = [] if a.depth else None
-    vel, upright, dt = play(a.robot, a.weights, a.envs, a.steps, a.vx, frames=frames, depth=depth)
+    vel, upright, dt = play(a.robot, a.weights, a.envs, a.steps, a.vx, frames=frames, depth=depth,
+                            depth_encoder=a.depth_encoder)
     if a.depth:
         np.savez_compressed(os.path.splitext(a.depth)[0] + ".npz", depth=np.stack(depth).astype(np.float32))
     if a.video:

@@ -5,7 +5,7 @@
 set -euo pipefail
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd "$ROOT/rapid-locomotion-rl_amd/csrc"
-ALL="lrl_env_dispatch.hip lrl_env_flat.hip lrl_env_mesh.hip lrl_env_mesh_tgs.hip lrl_aux.hip lrl_gae.hip lrl_gemm.hip lrl_ppo.hip lrl_curriculum_dev.hip lrl_render.hip lrl_depth.hip"
+ALL="lrl_env_dispatch.hip lrl_env_flat.hip lrl_env_mesh.hip lrl_env_mesh_tgs.hip lrl_aux.hip lrl_gae.hip lrl_gemm.hip lrl_ppo.hip lrl_curriculum_dev.hip lrl_render.hip lrl_depth.hip lrl_vision.hip"
 for f in ${@:-$ALL}; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast-honor-pragmas \
     -Xclang -target-feature -Xclang -packed-fp32-ops --cuda-device-only \
