@@ -724,6 +724,9 @@ int32_t lrl_sim_depth(lrl_sim* sim, const lrl_depth_camera* cam, int32_t first_e
                       int32_t only_reset, float* depth /* [num_envs][H][W] */, int32_t* ids /* or NULL */,
                       void* stream);
 
+/* The depth sensor model on top of these images (noise, edge loss, dropout, quantisation, latency:
+ * lrl_sim_depth_sense) is part of this ABI in a header of its own, include/lrl_depth_sense.h, included below. */
+
 /* ------------------------------------------------------------------------------------------
  * PPO numeric core.
  * ------------------------------------------------------------------------------------------ */
@@ -979,5 +982,7 @@ double lrl_np_sum_f64(const double* a, int64_t n);
 
 /* the depth encoder's entry points (lrl_vision_*), part of this ABI, in a header of their own */
 #include "lrl_vision.h"
+/* the depth sensor model (lrl_depth_sensor, lrl_sim_depth_sense), likewise */
+#include "lrl_depth_sense.h"
 
 #endif /* LRL_H_ */

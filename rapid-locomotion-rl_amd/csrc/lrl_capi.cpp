@@ -950,6 +950,34 @@ int32_t lrl_sim_depth(lrl_sim* s, const lrl_depth_camera* cam, int32_t first_env
   return 0;
 }
 
+int32_t lrl_sim_depth_sense(lrl_sim* s, const lrl_depth_sensor* p, int32_t first_env, int32_t num_envs, int32_t mode,
+                            uint64_t frame, const float* depth, const float* uniforms, float* ring, int32_t* head,
+                            int32_t* latency, float* sensed, void* stream) {
+  if (!s) return fail(LRL_E_INVALID, "null sim");
+  if (!p) return fail(LRL_E_INVALID, "lrl_sim_depth_sense: null sensor");
+  if (!depth || !ring || !head || !latency || !sensed)
+    return fail(LRL_E_INVALID, "lrl_sim_depth_sense: null depth, ring, head, latency or sensed buffer");
+  if (first_env < 0 || num_envs < 0 || first_env > s->S.n || num_envs > s->S.n - first_env)
+    return fail(LRL_E_INVALID, "env range [%d, %d + %d) outside the sim's %d envs", first_env, first_env, num_envs, s->S.n);
+  if (p->width < 1 || p->width > 1024 || p->height < 1 || p->height > 1024)
+    return fail(LRL_E_INVALID, "depth image size %d x %d outside [1, 1024]", p->width, p->height);
+  if (!(p->near >= 0.f && p->near < p->far && p->far < 3.0e38f))
+    return fail(LRL_E_INVALID, "near %g, far %g outside 0 <= near < far < 3e38", p->near, p->far);
+  const float nonneg[4] = {p->noise_a, p->noise_b, p->edge_thresh, p->quant};
+  for (float x : nonneg)
+    if (!(x >= 0.f && fabsf(x) < INFINITY))
+      return fail(LRL_E_INVALID, "noise_a %g, noise_b %g, edge_thresh %g, quant %g: negative or not finite", p->noise_a,
+                  p->noise_b, p->edge_thresh, p->quant);
+  if (!(p->dropout_p >= 0.f && p->dropout_p <= 1.f)) return fail(LRL_E_INVALID, "dropout_p %g outside [0, 1]", p->dropout_p);
+  if (!(fabsf(p->invalid_value) < INFINITY)) return fail(LRL_E_INVALID, "invalid_value %g is not finite", p->invalid_value);
+  if (p->latency_min < 0 || p->latency_min > p->latency_max || p->latency_max > 15)
+    return fail(LRL_E_INVALID, "latency [%d, %d] outside 0 <= min <= max <= 15", p->latency_min, p->latency_max);
+  if (mode < LRL_SENSE_PUSH || mode > LRL_SENSE_FILL) return fail(LRL_E_INVALID, "lrl_sim_depth_sense: mode %d outside 0..2", mode);
+  HIPCHECK(lrl_launch_depth_sense(&s->S, p, first_env, num_envs, mode, frame, depth, uniforms, ring, head, latency, sensed,
+                                  (hipStream_t)stream));
+  return 0;
+}
+
 int32_t lrl_sim_shift_history(lrl_sim* s, void* stream) {
   if (!s) return fail(LRL_E_INVALID, "null sim");
   HIPCHECK(lrl_launch_shift_history(&s->S, s->hk.p.num_obs, s->hk.p.num_history * s->hk.p.num_obs, 1,

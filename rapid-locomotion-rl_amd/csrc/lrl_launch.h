@@ -54,6 +54,9 @@ hipError_t lrl_launch_record_state(const KState*, int32_t, int32_t, int32_t*, hi
 // lrl_depth.hip: num_envs workgroups, image b of env first_env + b
 hipError_t lrl_launch_depth(const KParams*, const KState*, const KRender*, const lrl_depth_camera*, int32_t, int32_t,
                             int32_t, float*, int32_t*, hipStream_t);
+// lrl_depth_sense.hip: num_envs workgroups, row b of every array of env first_env + b
+hipError_t lrl_launch_depth_sense(const KState*, const lrl_depth_sensor*, int32_t, int32_t, int32_t, uint64_t,
+                                  const float*, const float*, float*, int32_t*, int32_t*, float*, hipStream_t);
 hipError_t lrl_launch_metrics(const KParams*, const KState*, const KMetrics*, int, hipStream_t);
 hipError_t lrl_launch_metrics_clear(const KState*, const KMetrics*, hipStream_t);
 hipError_t lrl_launch_metrics_reduce(const KParams*, const KState*, const KMetrics*, int32_t, int32_t, double*,

@@ -215,6 +215,18 @@ class LrlDepthCamera(C.Structure):
 DEPTH_NO_ROBOT = 1
 
 
+class LrlDepthSensor(C.Structure):
+    """lrl_depth_sensor (lrl_sim_depth_sense): the sensor model applied to the exact depth image."""
+    _fields_ = [("width", i32), ("height", i32), ("near", f32), ("far", f32), ("noise_a", f32), ("noise_b", f32),
+                ("dropout_p", f32), ("edge_thresh", f32), ("invalid_value", f32), ("quant", f32),
+                ("latency_min", i32), ("latency_max", i32)]
+
+
+# the LRL_SENSE_* enum of include/lrl.h (lrl_sim_depth_sense's mode; tests/test_depth_sensor_abi.py compares)
+SENSE_PUSH, SENSE_RESET_ONLY, SENSE_FILL = 0, 1, 2
+RNG_DEPTH = 8  # LRL_RNG_DEPTH (include/lrl_philox.h): the sensor's Philox stream
+
+
 PPO_CTRL_BYTES = 64  # sizeof(lrl_ppo_ctrl): double lr, double loss_sum[3], float mb[4], float x4
 
 
@@ -239,6 +251,8 @@ def _fill_array(arr, v):
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "lrl.h")
+# the depth sensor model's part of the ABI: a header of its own that lrl.h includes (lrl_sim_depth_sense)
+_SENSE_HEADER = os.path.join(os.path.dirname(_HEADER), "lrl_depth_sense.h")
 
 
 def source_hash():
@@ -261,6 +275,8 @@ MIRRORS = {"lrl_model": LrlModel, "lrl_env_params": LrlEnvParams, "lrl_group_par
            "lrl_ppo_net": LrlPpoNet, "lrl_ppo_batch": LrlPpoBatch, "lrl_ppo_hparams": LrlPpoHparams,
            "lrl_dev_curriculum": LrlDevCurriculum, "lrl_nav_state": LrlNavState, "lrl_gemm_desc": LrlGemmDesc,
            "lrl_camera": LrlCamera, "lrl_depth_camera": LrlDepthCamera}
+# (lrl_depth_sensor, like lrl_vision_net, is not among them: its entry point takes byref(LrlDepthSensor) as a plain
+# pointer; tests/test_depth_sensor_abi.py compares its layout with the header's)
 _SCALARS = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
             "float": C.c_float, "double": C.c_double}
 _RETURNS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "const char*": C.c_char_p}
@@ -302,7 +318,8 @@ _lib = None
 
 
 def lib():
-    """liblrl.so, loaded once, every function with the restype and argtypes include/lrl.h declares.  Raises (no
+    """liblrl.so, loaded once, every function with the restype and argtypes include/lrl.h (and the depth sensor
+    model's header it includes, include/lrl_depth_sense.h) declares.  Raises (no
     fallback) if it was not built, or was built from other sources than the ones in this tree (a stale binary)."""
     global _lib
     if _lib is None:
@@ -315,10 +332,11 @@ def lib():
         if built != want and not os.environ.get("LRL_LIB"):
             raise RuntimeError(f"{LIB_PATH} was built from other sources (hash {built}, tree {want}); "
                                "rebuild it: __graft_entry__.build()")
-        with open(_HEADER) as f:
-            for name, (restype, argtypes) in signatures(f.read()).items():
-                fn = getattr(L, name)
-                fn.restype, fn.argtypes = restype, argtypes
+        for header in (_HEADER, _SENSE_HEADER):
+            with open(header) as f:
+                for name, (restype, argtypes) in signatures(f.read()).items():
+                    fn = getattr(L, name)
+                    fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 

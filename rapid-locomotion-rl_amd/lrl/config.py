@@ -166,6 +166,32 @@ def add_depth_camera(cfg, **overrides):
     cfg.depth = _build(dict(_DEPTH, **overrides), "depth")
     return cfg
 
+
+# The depth sensor model's group (project-only, a group of its own: Cfg.depth keeps its nine keys).
+_DEPTH_SENSOR = dict(noise_a=0.001, noise_b=0.005, dropout_p=0.01, edge_thresh=0.1, invalid_value=None, quant=0.001,
+                     latency_frames=[0, 1])
+
+
+def add_depth_sensor(cfg, **overrides):
+    """Install ``cfg.depth_sensor``: a ``LeggedRobotEnv`` built from ``cfg`` (which also needs ``cfg.depth``,
+    add_depth_camera) then keeps ``env.depth_sensed`` beside the exact ``env.depth_images``: what a stereo depth camera
+    would deliver of them (lrl_sim_depth_sense, include/lrl.h states the model).  Fields: the range noise's standard
+    deviation ``noise_a + noise_b z^2`` in metres, ``dropout_p`` (share of pixels lost at random), ``edge_thresh``
+    (relative depth step to a 4-neighbour at which both sides are lost; 0: none), ``invalid_value`` (what a lost pixel
+    reads; None: the camera's ``far``), ``quant`` (range step in metres; 0: none) and ``latency_frames`` = [min, max]:
+    each episode draws a delay from it, counted in the camera's full refreshes.
+
+    The defaults are choices in the range data sheets of RealSense-class stereo cameras give (millimetre noise at
+    arm's length growing with the square of the range, about a percent of holes, one refresh of delay at most); they
+    are not measurements of any camera.  ``overrides`` replace them; an unknown key is an error."""
+    unknown = set(overrides) - set(_DEPTH_SENSOR)
+    if unknown:
+        raise KeyError(f"add_depth_sensor: unknown field(s) {sorted(unknown)}; known: {', '.join(_DEPTH_SENSOR)}")
+    vals = dict(_DEPTH_SENSOR, **overrides)
+    vals["latency_frames"] = list(vals["latency_frames"])
+    cfg.depth_sensor = _build(vals, "depth_sensor")
+    return cfg
+
 _LEG_ORDER = ("FL", "RL", "FR", "RR")
 
 

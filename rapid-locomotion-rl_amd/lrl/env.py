@@ -384,6 +384,31 @@ class LeggedRobotEnv:
             self._depth_step = 0  # steps taken with the sensor: a full refresh when it is a multiple of the interval
             self.depth_images = torch.full((self.num_envs, max(cam.height, 0), max(cam.width, 0)), cam.far,
                                            dtype=torch.float32, device=self.device)
+        # the depth sensor model (the project-only group Cfg.depth_sensor, lrl.config.add_depth_sensor): depth_sensed is
+        # what a real camera would deliver of depth_images.  Without the group: no attribute, buffer or launch.
+        self._depth_sensor = None
+        ds = getattr(cfg, "depth_sensor", None)
+        if ds is not None:
+            if dc is None:
+                raise ValueError("Cfg.depth_sensor needs the camera it models: the cfg has no Cfg.depth group "
+                                 "(lrl.config.add_depth_camera)")
+            lat = [int(x) for x in ds.latency_frames]
+            if len(lat) != 2 or not 0 <= lat[0] <= lat[1] <= 15:
+                raise ValueError(f"Cfg.depth_sensor.latency_frames must be [min, max] with 0 <= min <= max <= 15, "
+                                 f"got {list(ds.latency_frames)}")
+            sen = _abi.LrlDepthSensor()
+            sen.width, sen.height, sen.near, sen.far = cam.width, cam.height, cam.near, cam.far
+            sen.noise_a, sen.noise_b = float(ds.noise_a), float(ds.noise_b)
+            sen.dropout_p, sen.edge_thresh, sen.quant = float(ds.dropout_p), float(ds.edge_thresh), float(ds.quant)
+            sen.invalid_value = cam.far if ds.invalid_value is None else float(ds.invalid_value)
+            sen.latency_min, sen.latency_max = lat
+            self._depth_sensor = sen
+            shape = self.depth_images.shape
+            self.depth_sensed = torch.full(shape, cam.far, dtype=torch.float32, device=self.device)
+            self.depth_latency = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+            self._depth_ring = torch.full((self.num_envs, lat[1] + 1) + tuple(shape[1:]), cam.far,
+                                          dtype=torch.float32, device=self.device)
+            self._depth_head = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
 
         # ---- origins, DR draws at creation (legged_robot.py:1216-1231, 1385-1415, 519-542) ----
         self._set_env_origins()
@@ -1062,8 +1087,19 @@ class LeggedRobotEnv:
     def _depth_tick(self):
         """The depth camera's part of step(), after the step's resets and re-observation: every update_interval-th
         step (the first one included) redraws every env's image; the steps between redraw only the envs whose reset
-        flag is set, so no env shows its previous episode's view.  Two launches on the step's stream, no host read."""
-        self._depth_launch(only_reset=self._depth_step % self._depth_interval != 0)
+        flag is set, so no env shows its previous episode's view.  Two launches on the step's stream, no host read;
+        with Cfg.depth_sensor a third, which turns ``depth_images`` (left exact) into ``depth_sensed``."""
+        only_reset = self._depth_step % self._depth_interval != 0
+        self._depth_launch(only_reset=only_reset)
+        if self._depth_sensor is not None:
+            # the sensor model on the image just drawn (Cfg.depth_sensor): the first tick fills every env's ring, a
+            # full refresh pushes a frame (a reset env refills), the ticks between refill the reset envs only
+            mode = _abi.SENSE_FILL if self._depth_step == 0 else \
+                _abi.SENSE_RESET_ONLY if only_reset else _abi.SENSE_PUSH
+            _abi.check(self._L.lrl_sim_depth_sense(
+                self._sim, C.byref(self._depth_sensor), 0, self.num_envs, mode, self._depth_step,
+                self.depth_images.data_ptr(), None, self._depth_ring.data_ptr(), self._depth_head.data_ptr(),
+                self.depth_latency.data_ptr(), self.depth_sensed.data_ptr(), self._stream()))
         self._depth_step += 1
 
     @property

@@ -228,10 +228,16 @@ class DepthDistiller:
     ``collect(obs)`` after a step whose ``env.depth_refreshed`` is True appends every env's (image, extra, target) to
     device rings of ``capacity`` rows; ``update(n)`` runs n Adam steps on random minibatches (the rings are read in
     place through ``rows``); ``predict_obs(obs)`` swaps the scan columns for the encoder's output.  It reads from the
-    env and writes nothing to it."""
+    env and writes nothing to it.  ``sensed=True``: ``collect`` and ``predict_obs`` read ``env.depth_sensed``, the
+    sensor model's noisy, late images (lrl.config.add_depth_sensor), and an env without it is refused."""
 
-    def __init__(self, env, encoder, capacity=16384, batch_size=1024, lr=1e-3, native=None, seed=0):
+    def __init__(self, env, encoder, capacity=16384, batch_size=1024, lr=1e-3, native=None, seed=0, sensed=False):
         self.env, self.encoder = env, encoder
+        # sensed: read env.depth_sensed (the sensor model's images, Cfg.depth_sensor) in place of the exact ones
+        self.sensed = bool(sensed)
+        if self.sensed and getattr(env, "depth_sensed", None) is None:
+            raise ValueError("DepthDistiller(sensed=True): the env has no depth sensor model (the cfg has no "
+                             "depth_sensor group, lrl.config.add_depth_sensor)")
         self.first, self.num_scan = scan_columns(env)
         if encoder.out_dim != self.num_scan or encoder.extra_dim != self.first:
             raise ValueError(f"DepthDistiller: the encoder maps {encoder.extra_dim} extra columns to {encoder.out_dim}, "
@@ -251,9 +257,12 @@ class DepthDistiller:
         self.gen = torch.Generator(device=dev)
         self.gen.manual_seed(seed)
 
+    def _env_images(self):
+        return self.env.depth_sensed if self.sensed else self.env.depth_images
+
     def collect(self, obs, env_ids=None):
         """Append (depth image, extra, target) of every env (or of ``env_ids``) at the ring's head, wrapping."""
-        img = self.env.depth_images
+        img = self._env_images()
         if env_ids is not None:
             img, obs = img[env_ids], obs[env_ids]
         n = img.shape[0]
@@ -303,7 +312,7 @@ class DepthDistiller:
     def predict_obs(self, obs):
         """``obs`` with its scan columns replaced by the encoder's output from the env's current depth images."""
         extra = obs[:, :self.first]
-        img = self.env.depth_images
+        img = self._env_images()
         pred = self.encoder.forward_native(img, extra) if self.native else self.encoder(img, extra)
         out = obs.clone()
         out[:, self.first:] = pred

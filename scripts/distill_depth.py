@@ -33,8 +33,9 @@ from lrl.history import HistoryWrapper  # noqa: E402
 from lrl.ppo.actor_critic import ActorCritic  # noqa: E402
 
 
-def make_env(num_envs, device, seed=4321, depth=True):
-    """bench.py's bench_go1_rough env with the height scan on, and the depth camera"""
+def make_env(num_envs, device, seed=4321, depth=True, sensor=False):
+    """bench.py's bench_go1_rough env with the height scan on, and the depth camera (``sensor``: and its sensor
+    model, lrl.config.add_depth_sensor's defaults)"""
     cfg = lcfg.make_cfg()
     lcfg.config_go1(cfg)
     cfg.env.num_envs = num_envs
@@ -45,6 +46,8 @@ def make_env(num_envs, device, seed=4321, depth=True):
     cfg.env.num_observations = 42 + len(cfg.terrain.measured_points_x) * len(cfg.terrain.measured_points_y)
     if depth:
         lcfg.add_depth_camera(cfg)
+        if sensor:
+            lcfg.add_depth_sensor(cfg)
     return HistoryWrapper(LeggedRobotEnv(device, cfg=cfg, seed=seed, legacy_fork=False)), cfg
 
 
@@ -58,8 +61,9 @@ def train_policy(path, num_envs, iterations, device):
 
 
 def distill(ckpt, iterations=50, num_envs=4096, steps=25, updates=20, out_dir=".", log=None, device="cuda:0",
-            capacity=None, batch_size=1024, lr=1e-3):
-    env, cfg = make_env(num_envs, device)
+            capacity=None, batch_size=1024, lr=1e-3, sensor=False):
+    """``sensor``: distil from ``env.depth_sensed`` (noise, holes, quantisation, latency) instead of the exact images."""
+    env, cfg = make_env(num_envs, device, sensor=sensor)
     e = env.env
     ac = ActorCritic(cfg.env.num_observations, cfg.env.num_privileged_obs,
                      cfg.env.num_observations * cfg.env.num_observation_history, cfg.env.num_actions)
@@ -70,7 +74,8 @@ def distill(ckpt, iterations=50, num_envs=4096, steps=25, updates=20, out_dir=".
     enc = vision.DepthEncoder(h, w, scan, extra_dim=first, hidden=128, far=float(cfg.depth.far)).to(device)
     n_train = num_envs - max(num_envs // 10, 1)
     train_ids = torch.arange(n_train, device=device)
-    d = vision.DepthDistiller(e, enc, capacity=capacity or 4 * n_train, batch_size=batch_size, lr=lr)
+    d = vision.DepthDistiller(e, enc, capacity=capacity or 4 * n_train, batch_size=batch_size, lr=lr,
+                              sensed=sensor)
     obs = env.reset()
     lines = []
     t0 = time.perf_counter()
@@ -82,7 +87,8 @@ def distill(ckpt, iterations=50, num_envs=4096, steps=25, updates=20, out_dir=".
             obs, _, _, _ = env.step(actions)
             if e.depth_refreshed:
                 d.collect(obs["obs"], train_ids)
-                held.append(d.evaluate(e.depth_images[n_train:].contiguous(), obs["obs"][n_train:]))
+                img = e.depth_sensed if sensor else e.depth_images
+                held.append(d.evaluate(img[n_train:].contiguous(), obs["obs"][n_train:]))
         train_loss = d.update(updates)
         line = {"iteration": it, "rows": d.size, "train_loss": round(float(train_loss), 6),
                 "held_out_loss": round(float(torch.stack(held).mean()), 6) if held else None,
@@ -110,12 +116,14 @@ def main():
     ap.add_argument("--out-dir", default=".")
     ap.add_argument("--log", default=None, help="append the JSON lines to this file")
     ap.add_argument("--train-iterations", type=int, default=0)
+    ap.add_argument("--sensor", action="store_true", help="distil from the sensor model's images (env.depth_sensed)")
     a = ap.parse_args()
     if not os.path.exists(a.ckpt):
         if a.train_iterations <= 0:
             sys.exit(f"{a.ckpt} does not exist (--train-iterations K trains a policy to try the script on)")
         train_policy(a.ckpt, a.envs, a.train_iterations, "cuda:0")
-    path, lines = distill(a.ckpt, a.iterations, a.envs, a.steps, a.updates, a.out_dir, a.log)
+    path, lines = distill(a.ckpt, a.iterations, a.envs, a.steps, a.updates, a.out_dir, a.log,
+                          sensor=a.sensor)
     print(json.dumps({"saved": path, "first_held_out_loss": lines[0]["held_out_loss"],
                       "last_held_out_loss": lines[-1]["held_out_loss"]}))
 

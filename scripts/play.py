@@ -9,14 +9,15 @@ the actor (``ActorCritic.act_student_fused``, the native GEMM chain).  A constan
 (and plotted with ``--plot out.png``).  ``--video OUT`` writes one frame of env 0 per policy step (the headless
 camera of ``env.render()``: the collision model plus link capsules) as ``OUT.npz``, and ``OUT.gif`` when PIL is installed.
 ``--depth OUT`` gives every env the egocentric depth camera (lrl.config.add_depth_camera's defaults) and saves env 0's
-image after every policy step as ``OUT.npz``: ``depth`` float32 [T, H, W], metres.
+image after every policy step as ``OUT.npz``: ``depth`` float32 [T, H, W], metres.  With ``--depth-sensor`` the env also
+runs the depth sensor model (lrl.config.add_depth_sensor's defaults) and ``OUT.npz`` holds ``depth_sensed`` beside it.
 ``--depth-encoder ENC.pt`` (scripts/distill_depth.py's ``depth_encoder_last.pt``; needs ``--weights`` of a policy trained
 with the 187-column height scan): the env is the rough trimesh with the scan and the depth camera on, and the policy acts
 on ``DepthDistiller.predict_obs(obs)`` — the scan columns it sees, now and in its observation history, are the encoder's
 output from the depth image, not the simulator's scan.
 
   python scripts/play.py [--robot mc|go1] [--weights ac_weights.pt] [--envs 64] [--steps 1000] [--vx 1.0] [--video OUT]
-                         [--depth OUT] [--depth-encoder ENC.pt]
+                         [--depth OUT [--depth-sensor]] [--depth-encoder ENC.pt]
 """
 import argparse
 import json
@@ -35,7 +36,7 @@ from lrl.history import HistoryWrapper  # noqa: E402
 from lrl.ppo.actor_critic import ActorCritic  # noqa: E402
 
 
-def load_env(robot, num_envs, device, depth=False, scan=False):
+def load_env(robot, num_envs, device, depth=False, scan=False, depth_sensor=False):
     cfg = lcfg.make_cfg()
     (lcfg.config_mini_cheetah if robot == "mc" else lcfg.config_go1)(cfg)
     dr = cfg.domain_rand
@@ -52,6 +53,8 @@ def load_env(robot, num_envs, device, depth=False, scan=False):
         cfg.env.num_observations = 42 + len(cfg.terrain.measured_points_x) * len(cfg.terrain.measured_points_y)
     if depth:
         lcfg.add_depth_camera(cfg)
+        if depth_sensor:
+            lcfg.add_depth_sensor(cfg)
     return HistoryWrapper(LeggedRobotEnv(device, cfg=cfg)), cfg
 
 
@@ -90,12 +93,15 @@ def depth_observer(path, env, device):
 
 
 def play(robot="mc", weights=None, num_envs=64, steps=1000, vx=1.0, vy=0.0, wz=0.0, device="cuda:0", frames=None,
-         depth=None, depth_encoder=None):
+         depth=None, depth_encoder=None, depth_sensed=None):
     """``frames``: a list that receives env 0's rendered frame (numpy uint8 [240, 360, 4]) after every policy step;
     ``depth``: a list that receives env 0's depth image (numpy float32 [H, W]) after every policy step;
+    ``depth_sensed`` (with ``depth``): a list that receives what the sensor model delivers of it (env.depth_sensed);
     ``depth_encoder``: a saved DepthEncoder, the policy then acts on its prediction of the height scan."""
+    if depth_sensed is not None and depth is None:
+        raise ValueError("play: depth_sensed needs depth")
     env, cfg = load_env(robot, num_envs, device, depth=depth is not None or depth_encoder is not None,
-                        scan=depth_encoder is not None)
+                        scan=depth_encoder is not None, depth_sensor=depth_sensed is not None)
     policy = load_policy(weights, cfg, device)
     e = env.env
     observe = depth_observer(depth_encoder, env, device) if depth_encoder else None
@@ -126,6 +132,8 @@ def play(robot="mc", weights=None, num_envs=64, steps=1000, vx=1.0, vy=0.0, wz=0
             frames.append(e.render())
         if depth is not None:
             depth.append(e.depth_images[0].cpu().numpy())
+        if depth_sensed is not None:
+            depth_sensed.append(e.depth_sensed[0].cpu().numpy())
     upright = (e.projected_gravity[:, 2] < -0.8).float().mean().item()
     e.close()
     return vel, upright, e.dt
@@ -143,15 +151,23 @@ def main():
     ap.add_argument("--depth", default=None, metavar="OUT", help="write env 0's depth images to OUT.npz")
     ap.add_argument("--depth-encoder", default=None, metavar="ENC.pt",
                     help="act on the depth encoder's height scan (needs --weights of a policy trained with the scan)")
+    ap.add_argument("--depth-sensor", action="store_true",
+                    help="with --depth: run the sensor model and store its images too (depth_sensed)")
     a = ap.parse_args()
     if a.depth_encoder and not a.weights:
         ap.error("--depth-encoder needs --weights: the default checkpoint's policy has no height scan")
+    if a.depth_sensor and not a.depth:
+        ap.error("--depth-sensor needs --depth OUT")
     frames = [] if a.video else None
     depth = [] if a.depth else None
+    sensed = [] if a.depth_sensor else None
     vel, upright, dt = play(a.robot, a.weights, a.envs, a.steps, a.vx, frames=frames, depth=depth,
-                            depth_encoder=a.depth_encoder)
+                            depth_encoder=a.depth_encoder, depth_sensed=sensed)
     if a.depth:
-        np.savez_compressed(os.path.splitext(a.depth)[0] + ".npz", depth=np.stack(depth).astype(np.float32))
+        arrays = dict(depth=np.stack(depth).astype(np.float32))
+        if sensed is not None:
+            arrays["depth_sensed"] = np.stack(sensed).astype(np.float32)
+        np.savez_compressed(os.path.splitext(a.depth)[0] + ".npz", **arrays)
     if a.video:
         from ml_logger import ML_Logger
         out = os.path.abspath(os.path.splitext(a.video)[0])
