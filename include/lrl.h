@@ -821,7 +821,6 @@ int32_t lrl_ppo_act(const lrl_ppo_net* net, const float* params, const float* ob
                     float* actions,
                     float* mu, float* values, float* logp, const lrl_rollout_store* store, int32_t store_row,
                     void* workspace, void* stream);
-
 /* Student act (actor_critic.py:160-164, the eval-env path of Runner.learn __init__.py:130-135 and the
  * deployed policy of play.py): latent = adaptation_module(hist) (630 -> 256 -> 32 -> 18, ELU), mean =
  * actor_body([obs, latent]) — deterministic, no sampling.  hist rows at pitch hist_ld (0 = num_hist; a
@@ -984,5 +983,7 @@ double lrl_np_sum_f64(const double* a, int64_t n);
 #include "lrl_vision.h"
 /* the depth sensor model (lrl_depth_sensor, lrl_sim_depth_sense), likewise */
 #include "lrl_depth_sense.h"
+/* the history shift done by the rollout act (lrl_ppo_act_shift, lrl_sim_history_preshifted), likewise */
+#include "lrl_history_shift.h"
 
 #endif /* LRL_H_ */

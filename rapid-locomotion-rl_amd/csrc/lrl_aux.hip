@@ -300,9 +300,10 @@ __global__ __launch_bounds__(256) void extras_snapshot_kernel(const KParams* __r
 // append 0: the first H - NO floats only (hist[:, :H-NO] = hist[:, NO:]) — the shift half of the HistoryWrapper.step
 // update, launched by lrl_sim_step before the env kernel, which then writes the newest slot from its obs tile (a
 // bandwidth-shaped launch of 4096 workgroups instead of a latency-bound pass in the env kernel's single waves)
-__global__ void shift_history_kernel(KState S, int NO, int H, int append) {
+// first: the env row of workgroup 0 (lrl_sim_step after lrl_sim_history_preshifted: the rows below it are shifted already)
+__global__ void shift_history_kernel(KState S, int NO, int H, int append, int first) {
   extern __shared__ float row[];
-  const int e = blockIdx.x;
+  const int e = first + blockIdx.x;
   if (e >= S.n) return;
   float* h = S.hist + (size_t)e * H;
   const float* o = S.obs + (size_t)e * NO;
@@ -548,8 +549,9 @@ hipError_t lrl_launch_garbage(uint32_t mode, uint32_t pat, hipStream_t st) {
   if (mode & 2u) hipLaunchKernelGGL(lrl::garbage_vgpr_kernel, dim3(8192), dim3(64), 0, st, pat);
   return hipGetLastError();
 }
-hipError_t lrl_launch_shift_history(const KState* S, int NO, int H, int append, hipStream_t st) {
-  hipLaunchKernelGGL(lrl::shift_history_kernel, dim3(S->n), dim3(128), H * sizeof(float), st, *S, NO, H, append);
+hipError_t lrl_launch_shift_history(const KState* S, int NO, int H, int append, int first, hipStream_t st) {
+  if (first >= S->n) return hipSuccess;
+  hipLaunchKernelGGL(lrl::shift_history_kernel, dim3(S->n - first), dim3(128), H * sizeof(float), st, *S, NO, H, append, first);
   return hipGetLastError();
 }
 hipError_t lrl_launch_randomize(const KState* S, int32_t first, int32_t end, const float* fr, const float* rr,

@@ -52,6 +52,7 @@ struct lrl_sim {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
   size_t ev_used = 0;
   uint32_t garbage_mode = 0, garbage_pat = 0;  // lrl_debug_sim_garbage
+  int32_t hist_preshifted = 0;  // lrl_sim_history_preshifted: rows the next LRL_STEP_HISTORY step does not shift
   KRender rt;  // lrl_sim_render's model tables
   // evaluation metrics (lrl_sim_metrics_*): the tables' own allocation (null until first enabled) and the step's switch
   void* metrics_mem = nullptr;
@@ -558,9 +559,13 @@ int32_t lrl_sim_step(lrl_sim* s, const float* actions, uint32_t flags, void* str
     return fail(LRL_E_INVALID, "push_robots on but injected push uniforms not set");
   if (s->hk.p.terrain_mesh && !s->hk.terr_vtx) return fail(LRL_E_INVALID, "terrain_mesh set but no lrl_sim_set_terrain");
   s->step_counter += 1;  // common_step_counter (legged_robot.py:153)
-  if (flags & LRL_STEP_HISTORY)  // HistoryWrapper.step's shift; the env kernel appends the step's obs row
-    HIPCHECK(lrl_launch_shift_history(&s->S, s->hk.p.num_obs, s->hk.p.num_history * s->hk.p.num_obs, 0,
+  if (flags & LRL_STEP_HISTORY) {  // HistoryWrapper.step's shift; the env kernel appends the step's obs row
+    // (rows below hist_preshifted were shifted by the act that copied them: lrl_sim_history_preshifted, one step only)
+    const int first = s->hist_preshifted;
+    s->hist_preshifted = 0;
+    HIPCHECK(lrl_launch_shift_history(&s->S, s->hk.p.num_obs, s->hk.p.num_history * s->hk.p.num_obs, 0, first,
                                       (hipStream_t)stream));
+  }
   if (s->garbage_mode) HIPCHECK(lrl_launch_garbage(s->garbage_mode, s->garbage_pat, (hipStream_t)stream));
   std::pair<hipEvent_t, hipEvent_t>* tp = nullptr;
   if (s->timing) {
@@ -980,8 +985,15 @@ int32_t lrl_sim_depth_sense(lrl_sim* s, const lrl_depth_sensor* p, int32_t first
 
 int32_t lrl_sim_shift_history(lrl_sim* s, void* stream) {
   if (!s) return fail(LRL_E_INVALID, "null sim");
-  HIPCHECK(lrl_launch_shift_history(&s->S, s->hk.p.num_obs, s->hk.p.num_history * s->hk.p.num_obs, 1,
+  HIPCHECK(lrl_launch_shift_history(&s->S, s->hk.p.num_obs, s->hk.p.num_history * s->hk.p.num_obs, 1, 0,
                                     (hipStream_t)stream));
+  return 0;
+}
+
+int32_t lrl_sim_history_preshifted(lrl_sim* s, int32_t rows) {
+  if (!s) return fail(LRL_E_INVALID, "null sim");
+  if (rows < 0 || rows > s->S.n) return fail(LRL_E_INVALID, "lrl_sim_history_preshifted: rows %d outside [0, %d]", rows, s->S.n);
+  s->hist_preshifted = rows;
   return 0;
 }
 

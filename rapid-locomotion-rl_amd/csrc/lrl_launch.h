@@ -40,7 +40,7 @@ hipError_t lrl_launch_rigid_body(const KParams*, const KState*, const int32_t*, 
                                  hipStream_t);
 hipError_t lrl_launch_extras_snapshot(const KParams*, const KState*, const int32_t*, const int32_t*, const float*, float*,
                                       hipStream_t);
-hipError_t lrl_launch_shift_history(const KState*, int, int, int, hipStream_t);
+hipError_t lrl_launch_shift_history(const KState*, int, int, int, int, hipStream_t);
 hipError_t lrl_launch_garbage(uint32_t mode, uint32_t pat, hipStream_t st);
 hipError_t lrl_launch_randomize(const KState*, int32_t, int32_t, const float*, const float*, const float*, const float*,
                                 uint32_t, hipStream_t);

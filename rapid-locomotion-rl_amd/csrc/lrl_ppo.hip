@@ -369,6 +369,8 @@ struct ActHeadArgs {
   lrl_rollout_store store;
   int store_row, do_store;
   float* xa_out;  // ENC_ONLY: the [obs | latent | 0] rows, pitch xs
+  float* hist_shift;  // == hist, writable: the storage copy also shifts the rows left by hist_slot floats (else NULL)
+  int hist_slot;
 };
 
 // rows [0, nrows) of src (pitch sld) -> dst (pitch dld), `cols` floats each, by the block's NT
@@ -404,6 +406,61 @@ __device__ __forceinline__ void copy_rows(const float* __restrict__ src, int64_t
       for (int u = 0; u < 8; ++u) {
         const int i = i0 + u * NT, r = i / cols, c = i - r * cols;
         if (i < n) dst[r * dld + c] = v[u];
+      }
+    }
+  }
+}
+
+// copy_rows that also shifts the source rows left by one slot in place: every loaded value goes to dst as in
+// copy_rows and, from column `slot` on, to src[r][c - slot] (the HistoryWrapper shift, hist[:, :cols - slot] =
+// hist[:, slot:]; the newest slot src[r][cols - slot:] is not written).  src and dst pitches as copy_rows'.
+// The shifted store of element i lands on element i - slot of the same row, which another thread — of another wave,
+// or of an earlier batch — loads.  So a batch's stores are issued only once every wave's loads of that batch have
+// returned: each wave waits on its own loads (vmcnt(0): a barrier alone lets a wave pass with loads in flight) and
+// then meets the workgroup at the barrier.  A store reaches only elements at or below its batch, never the next
+// batch's, so one barrier per batch is enough.  Every thread of the workgroup calls this with the same arguments
+// (the batch loop is uniform: its barrier is reached by all NT threads).
+template <int NT = HEAD_THREADS>
+__device__ __forceinline__ void copy_rows_shift(float* src, int64_t sld, float* dst, int64_t dld, int nrows, int cols,
+                                                int slot, int t) {
+  if (((((uintptr_t)src | (uintptr_t)dst) & 7) == 0) && (((sld | dld | cols | slot) & 1) == 0)) {
+    const int c2 = cols / 2, s2 = slot / 2, n = nrows * c2;
+    for (int b0 = 0; b0 < n; b0 += 8 * NT) {
+      float2 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = b0 + t + u * NT, r = i / c2, c = i - r * c2;
+        if (i < n) v[u] = reinterpret_cast<const float2*>(src + r * sld)[c];
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = b0 + t + u * NT, r = i / c2, c = i - r * c2;
+        if (i < n) {
+          reinterpret_cast<float2*>(dst + r * dld)[c] = v[u];
+          if (c >= s2) reinterpret_cast<float2*>(src + r * sld)[c - s2] = v[u];
+        }
+      }
+    }
+  } else {
+    const int n = nrows * cols;
+    for (int b0 = 0; b0 < n; b0 += 8 * NT) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = b0 + t + u * NT, r = i / cols, c = i - r * cols;
+        if (i < n) v[u] = src[r * sld + c];
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = b0 + t + u * NT, r = i / cols, c = i - r * cols;
+        if (i < n) {
+          dst[r * dld + c] = v[u];
+          if (c >= slot) src[r * sld + c - slot] = v[u];
+        }
       }
     }
   }
@@ -515,7 +572,8 @@ __global__ __launch_bounds__(HEAD_THREADS) void act_head_kernel(ActHeadArgs a) {
       copy_rows(a.priv + (int64_t)r0 * a.np, a.np, a.store.priv + b * a.np, a.np, nrows, a.np, t);
     if (a.hist && a.store.hist) {
       const int hd = a.store.hist_dim, ld = a.store.hist_ld > hd ? a.store.hist_ld : hd;
-      copy_rows(a.hist + (int64_t)r0 * hd, hd, a.store.hist + b * ld, ld, nrows, hd, t);
+      if (a.hist_shift) copy_rows_shift(a.hist_shift + (int64_t)r0 * hd, hd, a.store.hist + b * ld, ld, nrows, hd, a.hist_slot, t);
+      else copy_rows(a.hist + (int64_t)r0 * hd, hd, a.store.hist + b * ld, ld, nrows, hd, t);
     }
   }
 }
@@ -721,6 +779,8 @@ struct FusedActArgs {
   lrl_rollout_store store;
   int store_row, do_store;
   float* xa_out;  // ENC_ONLY: the [obs | latent | 0] rows, pitch xs
+  float* hist_shift;  // == hist, writable: the storage copy also shifts the rows left by hist_slot floats (else NULL)
+  int hist_slot;
 };
 
 // Obs staging and the env-factor encoder for 16 * RB rows from r0: X = [obs | latent | 0] (pitch FA_XP, zero rows past
@@ -1055,7 +1115,12 @@ __global__ __launch_bounds__(ENC_ONLY ? FA_THREADS : OA_THREADS) void act_fused_
       if (a.hist && a.store.hist) {
         const int hd = a.store.hist_dim, ld = a.store.hist_ld > hd ? a.store.hist_ld : hd;
         const int h0 = grp * (OA_R / 2), hn = min(nrows, h0 + OA_R / 2) - h0;
-        if (hn > 0) copy_rows<OA_THREADS>(a.hist + (int64_t)(r0 + h0) * hd, hd, a.store.hist + (b + h0) * ld, ld, hn, hd, t);
+        if (hn > 0) {
+          if (a.hist_shift)
+            copy_rows_shift<OA_THREADS>(a.hist_shift + (int64_t)(r0 + h0) * hd, hd, a.store.hist + (b + h0) * ld, ld, hn, hd,
+                                        a.hist_slot, t);
+          else copy_rows<OA_THREADS>(a.hist + (int64_t)(r0 + h0) * hd, hd, a.store.hist + (b + h0) * ld, ld, hn, hd, t);
+        }
       }
     }
     FA_PROF(10)
@@ -1895,11 +1960,15 @@ extern "C" int lrl_debug_act_profile(unsigned long long* out, int reset) {
 #endif
 }
 
-extern "C" int32_t lrl_ppo_act(const lrl_ppo_net* net, const float* params, const float* obs, const float* priv,
-                               const float* hist, int32_t n, const float* eps, uint64_t seed, uint64_t counter,
-                               int64_t row_offset, float* actions, float* mu, float* values, float* logp, const lrl_rollout_store* store,
-                               int32_t store_row, void* workspace, void* stream) {
+// lrl_ppo_act, and lrl_ppo_act_shift with hist_shift (NULL: hist is read only, as lrl_ppo_act)
+static int32_t ppo_act(const lrl_ppo_net* net, const float* params, const float* obs, const float* priv,
+                       const float* hist, int32_t n, const float* eps, uint64_t seed, uint64_t counter,
+                       int64_t row_offset, float* actions, float* mu, float* values, float* logp, const lrl_rollout_store* store,
+                       int32_t store_row, void* workspace, void* stream, float* hist_shift, int32_t hist_slot) {
   if (int rc = check_net(net)) return rc;
+  if (hist_shift && (hist_shift != hist || !store || !store->hist || hist_slot <= 0 || store->hist_dim % hist_slot != 0))
+    return lrl_set_error(LRL_E_INVALID, "lrl_ppo_act_shift: hist_shift must be hist, with a history store and a slot "
+                                        "width that divides its hist_dim");
   if (!params || !obs || (!priv && !net->plain) || !actions || !workspace || n <= 0)
     return lrl_set_error(LRL_E_INVALID, "lrl_ppo_act: null argument or n <= 0");
   if (store && (!store->obs || (!store->priv && priv) || !store->actions || !store->values || !store->logp ||
@@ -1915,6 +1984,7 @@ extern "C" int32_t lrl_ppo_act(const lrl_ppo_net* net, const float* params, cons
     a.actions = actions; a.mu = mu; a.values = values; a.logp = logp;
     if (store) a.store = *store;
     a.store_row = store_row; a.do_store = store ? 1 : 0;
+    a.hist_shift = hist_shift; a.hist_slot = hist_slot;
   };
   // (a plain net — priv / hist may be NULL: they are only copied into the storage row when given — is the same chain
   // with no encoder, no planes and tanh; the fused kernel is built around the presets' encoder and is not taken)
@@ -1960,6 +2030,23 @@ extern "C" int32_t lrl_ppo_act(const lrl_ppo_net* net, const float* params, cons
   io(ah);
   hipLaunchKernelGGL(act_head_kernel, dim3((n + ACT_ROWS - 1) / ACT_ROWS), dim3(HEAD_THREADS), 0, st, ah);
   return hipGetLastError() == hipSuccess ? 0 : lrl_set_error(LRL_E_HIP, "lrl_ppo_act: launch failed");
+}
+
+extern "C" int32_t lrl_ppo_act(const lrl_ppo_net* net, const float* params, const float* obs, const float* priv,
+                               const float* hist, int32_t n, const float* eps, uint64_t seed, uint64_t counter,
+                               int64_t row_offset, float* actions, float* mu, float* values, float* logp, const lrl_rollout_store* store,
+                               int32_t store_row, void* workspace, void* stream) {
+  return ppo_act(net, params, obs, priv, hist, n, eps, seed, counter, row_offset, actions, mu, values, logp, store, store_row,
+                 workspace, stream, nullptr, 0);
+}
+
+extern "C" int32_t lrl_ppo_act_shift(const lrl_ppo_net* net, const float* params, const float* obs, const float* priv,
+                                     const float* hist, int32_t n, const float* eps, uint64_t seed, uint64_t counter,
+                                     int64_t row_offset, float* actions, float* mu, float* values, float* logp,
+                                     const lrl_rollout_store* store, int32_t store_row, void* workspace, void* stream,
+                                     float* hist_shift, int32_t hist_slot) {
+  return ppo_act(net, params, obs, priv, hist, n, eps, seed, counter, row_offset, actions, mu, values, logp, store, store_row,
+                 workspace, stream, hist_shift, hist_slot);
 }
 
 // ---- student act (actor_critic.py:160-164): latent = adaptation_module(hist), mean = actor_body([obs, latent]) ----

@@ -253,6 +253,8 @@ _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "lrl.h")
 # the depth sensor model's part of the ABI: a header of its own that lrl.h includes (lrl_sim_depth_sense)
 _SENSE_HEADER = os.path.join(os.path.dirname(_HEADER), "lrl_depth_sense.h")
+# the history shift done by the rollout act, likewise (lrl_ppo_act_shift, lrl_sim_history_preshifted)
+_SHIFT_HEADER = os.path.join(os.path.dirname(_HEADER), "lrl_history_shift.h")
 
 
 def source_hash():
@@ -318,8 +320,9 @@ _lib = None
 
 
 def lib():
-    """liblrl.so, loaded once, every function with the restype and argtypes include/lrl.h (and the depth sensor
-    model's header it includes, include/lrl_depth_sense.h) declares.  Raises (no
+    """liblrl.so, loaded once, every function with the restype and argtypes include/lrl.h (and the headers it
+    includes for the depth sensor model and the act's history shift, include/lrl_depth_sense.h and
+    include/lrl_history_shift.h) declares.  Raises (no
     fallback) if it was not built, or was built from other sources than the ones in this tree (a stale binary)."""
     global _lib
     if _lib is None:
@@ -332,7 +335,7 @@ def lib():
         if built != want and not os.environ.get("LRL_LIB"):
             raise RuntimeError(f"{LIB_PATH} was built from other sources (hash {built}, tree {want}); "
                                "rebuild it: __graft_entry__.build()")
-        for header in (_HEADER, _SENSE_HEADER):
+        for header in (_HEADER, _SENSE_HEADER, _SHIFT_HEADER):
             with open(header) as f:
                 for name, (restype, argtypes) in signatures(f.read()).items():
                     fn = getattr(L, name)

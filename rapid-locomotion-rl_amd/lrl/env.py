@@ -31,11 +31,16 @@ from .terrain import Terrain, convert_heightfield_to_trimesh
 # committed model table (lrl/robots/<name>.json) — no URDF is read at run time
 MINI_GYM_ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _SNAPSHOT_EXTRAS = os.environ.get("LRL_EXTRAS_SNAPSHOT", "1") != "0"
+# LRL_EXTRAS_SNAPSHOT=eager: the snapshot is launched by every step instead of on demand (A/B timing, and the check of
+# the on-demand form: the values are the same bits either way)
+_EAGER_EXTRAS = os.environ.get("LRL_EXTRAS_SNAPSHOT") == "eager"
 
 
 class _LazyExtras(dict):
-    """``extras`` dict whose per-step numpy entries (velocity_tracking_easy_env.py:48-62) are step-time snapshots: step
-    enqueues one device copy of the fields they read (lrl_sim_extras_snapshot, into a buffer of that step's own), and an
+    """``extras`` dict whose per-step numpy entries (velocity_tracking_easy_env.py:48-62) are step-time snapshots: one
+    device copy of the fields they read (lrl_sim_extras_snapshot, into a buffer of that step's own), enqueued when the
+    first of them is read or, if none has been by then, before the env next writes that state outside step (see
+    LeggedRobotEnv._register_extras), and an
     entry becomes a numpy array only when read (the reference pays 11 device->host syncs per step).  As in the
     reference, ``extras`` is one dict updated by every step, so reading a key after the next step gives the next
     step's values; an array read, or a ``copy()`` / ``dict(...)`` / ``items()`` taken, holds the step it came from."""
@@ -439,6 +444,8 @@ class LeggedRobotEnv:
         self.env_command_bins_t = torch.zeros(self.num_envs, device=self.device)
         self._ids_all = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
         self._due_next = None  # (episode_length_buf version, env ids due for command resampling next step)
+        self._extras_pending = None  # the last step's extras snapshot while nobody has asked for it (_register_extras)
+        self.extras_snapshot_launches = 0  # lrl_sim_extras_snapshot launches so far (host-side count)
         self._step_timer = None  # optional section timer of step() (scripts/step_timing.py)
         # pinned staging of the upstream-reset path's host->device data (ids, resampled commands, command bins)
         self._up = _Upload(self.device, 64 * self.num_envs + 4096) if str(self.device).startswith("cuda") else None
@@ -691,6 +698,7 @@ class LeggedRobotEnv:
         ``_ids_host``: the same ids as a numpy array when the caller already has them on the host; ``_ids32``: as a
         device int32 array; ``_bins_to``: a device float tensor that receives all envs' command bins (reset_idx's
         env_bins) in the same launch."""
+        self._settle_extras()
         if env_ids is not None and len(env_ids) == 0 and self._dist is None:  # (ranks join the collective update
             return  # with no envs of their own)
         if _ids_host is not None and len(_ids_host) == 0 and self._dist is None:
@@ -755,6 +763,7 @@ class LeggedRobotEnv:
         if actions.shape != (self.num_envs, self.num_actions):
             raise ValueError(f"actions must be [{self.num_envs}, {self.num_actions}], got {tuple(actions.shape)}")
         flags = _abi.STEP_PHYSICS | (_abi.STEP_HISTORY if _history else 0)
+        self._extras_pending = None  # this step replaces the last one's lazy extras: an unread snapshot is never taken
         if self._dev_path:
             return self._step_device(actions, flags)
         tm = self._step_timer  # scripts/step_timing.py: host time per section of this method (None: off)
@@ -832,7 +841,7 @@ class LeggedRobotEnv:
                "contact_states": (46, 4), "foot_positions": (50, 12), "body_pos": (62, 3), "torques": (65, 12)}
 
     def _register_extras(self, ex):
-        """The step's numpy extras as lazy reads of one device snapshot taken now (see _LazyExtras).
+        """The step's numpy extras as lazy reads of one device snapshot of the state the step left (see _LazyExtras).
         (LRL_EXTRAS_SNAPSHOT=0, a development switch for A/B timing: lazy reads of the live tensors instead.)"""
         n = self.num_envs
         if not _SNAPSHOT_EXTRAS:
@@ -846,11 +855,28 @@ class LeggedRobotEnv:
             for key, fn in live.items():
                 ex.set_lazy(key, lambda fn=fn: fn().cpu().numpy().copy())
             return
-        snap = torch.empty(self._EXTRAS_ROWS, n, device=self.device)
-        _abi.check(self._L.lrl_sim_extras_snapshot(self._sim, snap.data_ptr(), self._stream()))
+        # The snapshot is taken on demand: nothing the kernel reads changes between the end of step and the next call
+        # that writes sim state, so the copy is launched by the first read of a key, or by _settle_extras at the start
+        # of such a call (an external reset_idx, a state setter, ...), with the bits the eager copy had.  The next step
+        # replaces all eleven entries and drops a snapshot nobody asked for (a training rollout reads none).
+        # (A caller that writes a state tensor through its torch view — env.commands[:] = ... — and wants the step's
+        # value of that field from extras afterwards reads the key, or calls _settle_extras, before the write.)
+        pend = {"snap": None, "fns": {}}
+
+        def snapshot():
+            if pend["snap"] is None:
+                snap = torch.empty(self._EXTRAS_ROWS, n, device=self.device)
+                _abi.check(self._L.lrl_sim_extras_snapshot(self._sim, snap.data_ptr(), self._stream()))
+                self.extras_snapshot_launches += 1
+                pend["snap"] = snap
+                if self._extras_pending is pend:
+                    self._extras_pending = None
+            return pend["snap"]
+        pend["take"] = snapshot
         nf = len(self.feet_indices)
 
         def read(key):
+            snap = snapshot()
             r0, k = self._EXTRAS[key]
             if key == "contact_states":
                 return (snap[r0:r0 + nf].t() > 0.5).cpu().numpy().copy()
@@ -858,7 +884,21 @@ class LeggedRobotEnv:
                 return snap[r0:r0 + 3 * nf].t().reshape(n, nf, 3).cpu().numpy().copy()
             return snap[r0:r0 + k].t().cpu().numpy().copy()
         for key in self._EXTRAS:
-            ex.set_lazy(key, lambda key=key: read(key))
+            fn = pend["fns"][key] = lambda key=key: read(key)
+            ex.set_lazy(key, fn)
+        self._extras_pending = pend
+        if _EAGER_EXTRAS:
+            snapshot()
+
+    def _settle_extras(self):
+        """Take the last step's extras snapshot now if it is still owed: called before anything outside step writes
+        state the snapshot reads.  Owed means not yet taken and at least one of the step's lazy entries still installed
+        in ``extras`` (an entry read, overwritten or deleted is no longer one)."""
+        pend, self._extras_pending = self._extras_pending, None
+        if pend is not None and pend["snap"] is None:
+            lazy = self.extras._lazy
+            if any(lazy.get(key) is fn for key, fn in pend["fns"].items()):
+                pend["take"]()
 
     _INT32_MAX = 2 ** 31 - 1
 
@@ -1131,6 +1171,7 @@ class LeggedRobotEnv:
         """legged_robot.py:227-290; train and eval envs (env id >= num_train_envs) go through their own cfg
         for the command curriculum (_call_train_eval, :456-469) and their own episode logging.  (_ids_host / _ids32:
         the same ids on the host and as a device int32 array, from step's upload.)"""
+        self._settle_extras()
         env_ids = torch.as_tensor(env_ids, device=self.device)
         if env_ids.dtype not in (torch.int64, torch.int32):  # (int32 ids — the step's compaction — index as they are)
             env_ids = env_ids.long()
@@ -1342,12 +1383,14 @@ class LeggedRobotEnv:
 
     # ---- gymapi-style setters (data is already in place when written through the views) ----
     def set_actor_root_state_tensor_indexed(self, root_states, env_ids):
+        self._settle_extras()
         ids = torch.as_tensor(env_ids, device=self.device).to(torch.int32).contiguous()
         src = root_states.contiguous()
         _abi.check(self._L.lrl_sim_set_root_state_indexed(self._sim, src.data_ptr(), ids.data_ptr(), len(ids),
                                                           self._stream()))
 
     def set_dof_state_tensor_indexed(self, dof_pos, dof_vel, env_ids):
+        self._settle_extras()
         ids = torch.as_tensor(env_ids, device=self.device).to(torch.int32).contiguous()
         p, v = dof_pos.contiguous(), dof_vel.contiguous()
         _abi.check(self._L.lrl_sim_set_dof_state_indexed(self._sim, p.data_ptr(), v.data_ptr(), ids.data_ptr(),
@@ -1355,6 +1398,11 @@ class LeggedRobotEnv:
 
     def shift_history(self):
         _abi.check(self._L.lrl_sim_shift_history(self._sim, self._stream()))
+
+    def history_preshifted(self, rows):
+        """Rows [0, rows) of obs_history_buf are shifted already (PPO.act(..., shift_history=True) did it while copying
+        them into the rollout storage): the next step with the history flag shifts the other rows only.  One step."""
+        _abi.check(self._L.lrl_sim_history_preshifted(self._sim, int(rows)))
 
     # ---- recording hooks used by Runner.log_video (legged_robot.py:743-755, 1332-1383) ----
     # A video is one full episode of the env: the frames from the step of its first reset after start_recording to the

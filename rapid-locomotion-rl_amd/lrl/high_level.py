@@ -361,6 +361,7 @@ class HighLevelControlWrapper:
         with torch.no_grad():
             ll_actions = self.low_level_policy(self.ll_obs)
         self.ll_obs, self.ll_rew, self.ll_dones, self.ll_info = self.ll_env.step(ll_actions)
+        e._settle_extras()  # lrl_nav_end_step resets envs: the low-level step's extras hold the state before that
         t = e.cfg.terrain
         reset_args = (e._root_mode(), float(t.x_init_range), float(t.y_init_range) - float(t.x_init_range),
                       float(t.x_init_offset), float(t.y_init_offset), e._stream())

@@ -1,7 +1,10 @@
 """HistoryWrapper (mini_gym/envs/wrappers/history_wrapper.py:6-41) over LeggedRobotEnv.
 
-The 15-step observation history lives in the sim ([N, 15*num_obs] HBM buffer) and is shifted
-inside the fused step kernel (LRL_STEP_HISTORY), so ``step`` costs no extra launch.  Attribute
+The 15-step observation history lives in the sim ([N, 15*num_obs] HBM buffer).  ``step`` (LRL_STEP_HISTORY)
+shifts it with one small launch (shift_history_kernel) before the step kernel, which writes the newest slot
+from its observation tile; in Runner.learn's rollout the act that copies the rows into the rollout storage
+shifts them in the same pass (PPO.act(shift_history=True) + env.history_preshifted), and that launch goes
+away.  Attribute
 reads fall through to the wrapped env like gym 0.19's ``Wrapper.__getattr__``; attribute WRITES
 land on the wrapper (which is why ``Runner.learn(init_at_random_ep_len=True)`` does not reach the
 env in the reference either — SURVEY.md Q5).

@@ -203,11 +203,15 @@ class ActorCritic(nn.Module):
                                                   ws[1].data_ptr(), _abi.stream_of(dev)))
         return mean, latent
 
-    def act_fused(self, obs, priv, hist=None, eps=None, seed=0, counter=0, store=None, store_row=0, row_offset=0):
+    def act_fused(self, obs, priv, hist=None, eps=None, seed=0, counter=0, store=None, store_row=0, row_offset=0,
+                  shift_history=False):
         """PPO.act teacher path on the flat parameters (lrl_ppo_act: fp32-MFMA GEMM chain + one head
         kernel that samples, scores and writes the storage row).  Returns (actions, mu, values [N,1], logp [N]).
         The policy noise is keyed by (seed, counter, row_offset + row): row_offset is the global id of row 0 (the
-        rank's env_offset), so a sharded rollout samples what one process holding every env would."""
+        rank's env_offset), so a sharded rollout samples what one process holding every env would.
+        shift_history: the kernel that copies the history rows into the storage row also shifts them left by one
+        observation in place (lrl_ppo_act_shift: hist[:, :-num_obs] = hist[:, num_obs:], the newest slot untouched) —
+        the caller then tells the env (history_preshifted) that its next step need not."""
         n = obs.shape[0]
         dev = obs.device
         # (priv None: a plain net — lrl.hlp — acts on the observations alone)
@@ -224,6 +228,14 @@ class ActorCritic(nn.Module):
         values = torch.empty(n, 1, device=dev)
         logp = torch.empty(n, device=dev)
         priv_p, hist_p, eps_p = (t.data_ptr() if t is not None else None for t in (priv, hist, eps))
+        if shift_history:
+            if hist is None or store is None or not hist.is_contiguous():
+                raise ValueError("shift_history needs a contiguous history and a rollout store")
+            _abi.check(_abi.lib().lrl_ppo_act_shift(net, self._flat.data_ptr(), obs.data_ptr(), priv_p, hist_p, n, eps_p,
+                                                    seed, counter, row_offset, actions.data_ptr(), mu.data_ptr(),
+                                                    values.data_ptr(), logp.data_ptr(), store, store_row,
+                                                    ws[1].data_ptr(), _abi.stream_of(dev), hist_p, obs.shape[1]))
+            return actions, mu, values, logp
         _abi.check(_abi.lib().lrl_ppo_act(net, self._flat.data_ptr(), obs.data_ptr(), priv_p, hist_p, n, eps_p, seed,
                                           counter, row_offset, actions.data_ptr(), mu.data_ptr(), values.data_ptr(),
                                           logp.data_ptr(), store, store_row, ws[1].data_ptr(), _abi.stream_of(dev)))

@@ -121,13 +121,18 @@ class PPO:
     def train_mode(self):
         self.actor_critic.train()
 
-    def act(self, obs, privileged_obs, obs_history, eps=None):
+    def act(self, obs, privileged_obs, obs_history, eps=None, shift_history=False):
+        """shift_history (native act only, obs_history contiguous): obs_history is shifted left by one observation in
+        place after its rows went into storage — HistoryWrapper.step's shift, done by the launch that reads the rows
+        anyway; the caller passes the env's own buffer and calls env.history_preshifted before env.step."""
+        if shift_history and not (self.fused and obs_history.is_contiguous()):
+            raise ValueError("shift_history needs the native act and a contiguous history")
         if self.fused:
             self._act_counter += 1
             a, mu, v, lp = self.actor_critic.act_fused(
                 obs.contiguous(), privileged_obs.contiguous(), obs_history.contiguous(), eps=eps, seed=self.seed,
                 counter=self._act_counter, store=self._store, store_row=self.storage.step,
-                row_offset=self.row_offset)
+                row_offset=self.row_offset, shift_history=shift_history)
             t = self.transition
             t.actions, t.values, t.actions_log_prob, t.action_mean = a, v, lp, mu
             t.action_sigma = self.actor_critic.std.detach().expand_as(mu)

@@ -87,6 +87,7 @@ class Runner:
             self.env.episode_length_buf = torch.randint_like(self.env.episode_length_buf,
                                                              high=int(self.env.max_episode_length))
         n_train = self.env.num_train_envs
+        shift_ok = os.environ.get("LRL_ACT_SHIFT_HISTORY", "1") != "0"  # (=0: the env's step shifts every row, for A/B)
         obs_dict = self.env.get_observations()
         obs, priv, hist = obs_dict["obs"], obs_dict["privileged_obs"], obs_dict["obs_history"]
         self.alg.actor_critic.train()
@@ -94,7 +95,12 @@ class Runner:
         for it in range(self.current_learning_iteration, tot_iter):
             with torch.inference_mode():
                 for _ in range(self.num_steps_per_env):
-                    actions = self.alg.act(obs[:n_train], priv[:n_train], hist[:n_train])
+                    # the act shifts the history rows it copies into storage, the env's step only the others (the eval
+                    # envs'): asked for when the act is native and reads the env's own history buffer
+                    shift = shift_ok and self.alg.fused and self._is_env_history(hist, n_train)
+                    actions = self.alg.act(obs[:n_train], priv[:n_train], hist[:n_train], shift_history=shift)
+                    if shift:
+                        self.env.history_preshifted(n_train)
                     if self.env.num_envs > n_train:  # eval envs: teacher or student means (__init__.py:130-135)
                         actions = torch.cat((actions, self._eval_actions(obs, priv, hist, n_train, eval_expert)), 0)
                     obs_dict, rewards, dones, infos = self.env.step(actions)
@@ -125,6 +131,13 @@ class Runner:
         self.current_learning_iteration += num_learning_iterations
         if num_learning_iterations > 0:  # the reference always saves after the loop (__init__.py:246-265)
             self.save(tot_iter - 1)
+
+    def _is_env_history(self, hist, n_train):
+        """hist[:n_train] is the first n_train rows of the env's own history buffer, the one its step shifts."""
+        buf = getattr(self.env, "obs_history_buf", None)
+        return (isinstance(buf, torch.Tensor) and hasattr(self.env, "history_preshifted") and hist.is_contiguous()
+                and buf.is_contiguous() and hist.data_ptr() == buf.data_ptr() and hist.shape == buf.shape
+                and hist.dtype == torch.float32 and 0 < n_train <= buf.shape[0])
 
     def log_video(self, it):
         """__init__.py:267-286: every save_video_interval iterations start recording env 0 (and the first eval env), and
